@@ -14,7 +14,9 @@ Rows per GPU (unless --rows is given):
           in "gather" (with and without it); `value` is the scan, which is what a plan whose root consumes its
           shard in place (an aggregation) pays.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the line; --full adds the
+figures that take work of their own (end to end with the result on the host, the read-stream ceiling, the CPU baselines,
+and at N > 1 the exchange).  --dump-outputs DIR writes what the last timed step returned (see dump_outputs).
 """
 import argparse
 import hashlib
@@ -146,6 +148,49 @@ def median(xs):
     return 0.0 if n == 0 else (xs[n // 2] if n % 2 else 0.5 * (xs[n // 2 - 1] + xs[n // 2]))
 
 
+DUMP_BUDGET_BYTES = 60_000_000     # every file of one dump together, .npy headers included, stays under 64 MB
+DUMP_SEED = 20241016
+
+
+def dump_outputs(path, res, rank, world):
+    """--dump-outputs: what the caller of the timed path receives -- the row count and every output column -- as float64
+    .npy files: count.npy, rows.npy (the result rows written), out<i>.npy (values, 0 where NULL) and out<i>_valid.npy for a
+    nullable column (STRING columns as dictionary codes, BOOLEAN as 0 / 1).  A result larger than the budget is written as a
+    sample of rows drawn by a fixed seed from the row count alone, so two builds that compute the same result write the same
+    files.  At N > 1 every rank writes its own shard's result, prefixed rank<r>_, within an equal share of the budget."""
+    import numpy as np
+    from queryengine_amd.datatypes import DataType
+    os.makedirs(path, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    n, ncols = res.count, res.ncols
+    cap = DUMP_BUDGET_BYTES // world // (8 * (1 + 2 * ncols))   # per row: its index, each column's value and validity
+    if n > cap:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap, replace=False))
+    else:
+        rows = np.arange(n, dtype=np.int64)
+
+    def bits(words, idx):
+        return ((words[idx >> 6] >> (idx & 63).astype(np.uint64)) & np.uint64(1)).astype(bool)
+
+    h = res.to_host().wait()          # the library's pinned staging: the columns are sampled in place
+    try:
+        np.save(os.path.join(path, prefix + "count.npy"), np.array([n], dtype=np.float64))
+        np.save(os.path.join(path, prefix + "rows.npy"), rows.astype(np.float64))
+        for c in range(ncols):
+            data, valid_words = h.column_views(c)
+            if DataType(res.view(c).type) == DataType.BOOLEAN:
+                vals = bits(data, rows).astype(np.float64)
+            else:
+                vals = data[rows].astype(np.float64)
+            if valid_words is not None:
+                valid = bits(valid_words, rows)
+                vals[~valid] = 0.0
+                np.save(os.path.join(path, f"{prefix}out{c}_valid.npy"), valid.astype(np.float64))
+            np.save(os.path.join(path, f"{prefix}out{c}.npy"), vals)
+    finally:
+        h.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -153,17 +198,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)   # the first executions of a plan also time its kernel geometries
     ap.add_argument("--rows", type=int, default=None, help="rows per GPU (default: see the module docstring)")
     ap.add_argument("--workload", default="config2", choices=["config1", "config2", "config3", "config4", "config2_swapped"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: end to end with the result on the host, the read-stream "
+                         "ceiling, the CPU baselines and, when --gpus > 1, the exchange")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result to DIR as float64 .npy files (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--tuning", default="", help="comma separated kernel tuning knobs (qe_options.tuning, DESIGN.md 3.1a)")
     ap.add_argument("--exec-mode", default="fused", choices=["fused", "per_node"])
     ap.add_argument("--selectivity", type=float, default=None, help="config2 only: target selectivity (changes the literals)")
-    ap.add_argument("--null-pct", type=int, default=0, help="config2 only: ~this % of NULLs in every input column (validity bitmaps "
+    ap.add_argument("--null-pct", type=int, default=0, help="config2 only: ~this %% of NULLs in every input column (validity bitmaps "
                     "are read, nullable outputs are packed): SURVEY 8(d)'s nullable variant")
-    ap.add_argument("--gather", action="store_true", help="time the materialising exchange too (default when --gpus > 1)")
+    ap.add_argument("--gather", action="store_true", help="time the materialising exchange too (default with --full when --gpus > 1)")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--profile-run", action="store_true",
                     help="under rocprofv3: exactly warmup + steps passes of the hot path and nothing else on the device")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -222,11 +274,13 @@ def main():
             r = E.filter_project(ctx, batch, cf, cp)
             r.free()
 
-    def step():
+    def step(keep=False):
         r = E.filter_project(ctx, batch, cf, cp)   # returns after the result count is known on the host
         n = r.count
+        if keep:                                   # --dump-outputs: the last timed step's result is read after the clock stops
+            return n, r
         r.free()                                   # buffers go back to the context pool (re-open pattern)
-        return n
+        return n, None
 
     def barrier():
         if world > 1:
@@ -236,14 +290,16 @@ def main():
 
     nout = 0
     for _ in range(args.warmup):
-        nout = step()
+        nout, _ = step()
     ctx.reset_kernel_time()
     step_ms, kern_ms = [], []
+    last = None
     barrier()
     t0 = time.perf_counter()
     tprev = t0
-    for _ in range(args.steps):
-        nout = step()                              # ends with the result count on the host: a step boundary is a sync
+    for i in range(args.steps):
+        # ends with the result count on the host: a step boundary is a sync
+        nout, last = step(keep=args.dump_outputs is not None and i == args.steps - 1)
         tnow = time.perf_counter()
         step_ms.append((tnow - tprev) * 1e3)
         tprev = tnow
@@ -251,6 +307,11 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     _, kernel_ms_total, launches = ctx.kernel_time()
+    if last is not None:
+        try:
+            dump_outputs(args.dump_outputs, last, rank, world)
+        finally:
+            last.free()
 
     t = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
     cnt = torch.tensor([nout], dtype=torch.int64, device="cpu" if rehearsal else "cuda")
@@ -265,7 +326,7 @@ def main():
     # pays for it and is not the minimum), what a JVM host wraps as MemorySegments; e2e_with_d2h_pageable_ms: the columns copied
     # into the CALLER's pageable buffers (qe_result_column_to_host: pinned chunks + a few memcpy threads)
     e2e_ms, e2e_pageable_ms = None, None
-    if not args.profile_run:
+    if args.full and not args.profile_run:
         try:
             import ctypes as C
             import numpy as np
@@ -305,7 +366,7 @@ def main():
         alg_bytes = wl.algorithmic_bytes(nrows, nout)
         achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
         stream_gbps = None
-        if not args.profile_run:
+        if args.full and not args.profile_run:
             try:
                 stream_gbps = ctx.stream_read_bandwidth(min(8 << 30, max(1 << 28, nrows * 8)), 5)
             except Exception:
@@ -374,7 +435,7 @@ def main():
                                  "the fraction of peak the kernel really sustains", "algorithmic_bytes_per_launch": alg_bytes,
                          "measured_stream_read_gbps": stream_gbps},
         }
-        if not args.no_cpu_baseline and world == 1 and not args.profile_run:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.profile_run:
             out["cpu_baseline"] = cpu_baseline(wl)
     else:
         out = None
@@ -402,7 +463,7 @@ def main():
     # a rehearsal (N ranks on ONE GPU) runs the exchange only when the caller names a transport that accepts several ranks
     # per device (QE_RCCL_LIBRARY; RCCL itself refuses that)
     exchange_possible = not rehearsal or world == 1 or bool(os.environ.get("QE_RCCL_LIBRARY"))
-    if (args.gather or world > 1) and not args.no_gather and not args.profile_run and exchange_possible:
+    if (args.gather or (args.full and world > 1)) and not args.no_gather and not args.profile_run and exchange_possible:
         try:
             from queryengine_amd import distributed as QD
             if world > 1:

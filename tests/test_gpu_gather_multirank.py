@@ -84,7 +84,7 @@ def test_bench_rehearsal_two_ranks_runs_the_exchange(native_lib):
     env = dict(os.environ, QE_BENCH_REHEARSAL="1", QE_RCCL_LIBRARY=TRANSPORT, QE_TEST_TRANSPORT_TIMEOUT_S="90")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--rows", "40000000", "--no-cpu-baseline"]
+           "--rows", "40000000", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

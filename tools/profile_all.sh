@@ -34,7 +34,7 @@ for C in $ORDER; do
     D=$OUT/$C; mkdir -p $D
     SCRIPT=$ROOT/${CMD%% *}; ARGS=${CMD#* }; [ "$ARGS" == "$CMD" ] && ARGS=""
     PLAIN=""; PROF=""
-    if [[ $CMD == bench.py* ]]; then PLAIN="--steps 10 --warmup 8 --no-cpu-baseline"; PROF="--steps 5 --warmup 2 --profile-run"; fi
+    if [[ $CMD == bench.py* ]]; then PLAIN="--steps 10 --warmup 8 --no-cpu-baseline --full"; PROF="--steps 5 --warmup 2 --profile-run"; fi
     echo "== $C: $CMD"
     timeout -k 10 300 python3 $SCRIPT $ARGS $PLAIN > $D/plain.out 2> $D/plain.err || { echo "$C: plain run failed"; tail -3 $D/plain.err; continue; }
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -- python3 $SCRIPT $ARGS $PROF > $D/trace.out 2> $D/trace.err || echo "$C: kernel-trace pass failed"
