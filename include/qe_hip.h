@@ -203,6 +203,35 @@ int32_t qe_csv_column(const qe_csv_table *table, int32_t col, qe_col_desc *out);
 int32_t qe_csv_pin(qe_ctx *ctx, const qe_csv_table *table, qe_batch **out);
 void qe_csv_free(qe_ctx *ctx, qe_csv_table *table);
 
+/* The same conversion with the parsing on the device: the header is resolved on the host, the text after it goes to HBM
+ * once, and kernels find the records and fields and convert them straight into the batch's device columns (DESIGN.md
+ * 3.6).  Same rules, same batch as qe_csv_parse + qe_csv_pin, or the same status and error text: wherever the device
+ * cannot prove that it reads the text as the host parser does (a '"' that is not a field's enclosing quote, an
+ * unterminated quote, a malformed number), the whole input goes through qe_csv_parse + qe_csv_pin instead.  The batch owns
+ * its device columns and dictionaries.  A planning-only context fails with QE_ERR_HIP; a text larger than free device
+ * memory with QE_ERR_OOM.  The file variant reads the file in chunks through pinned staging, the read of one chunk beside
+ * the copy of the previous one. */
+int32_t qe_csv_parse_device(qe_ctx *ctx, const char *utf8, size_t nbytes, int32_t nfields, const char *const *names,
+                            const int32_t *types, qe_batch **out);
+int32_t qe_csv_parse_file_device(qe_ctx *ctx, const char *path, int32_t nfields, const char *const *names,
+                                 const int32_t *types, qe_batch **out);
+/* what the last qe_csv_parse*_device call on this context did */
+typedef struct {
+    int64_t text_bytes;            /* bytes of the input */
+    int64_t nrows;
+    int64_t host_patched_fields;   /* DOUBLE fields the device left to the host converter (hexadecimal, > 19 digits) */
+    int32_t host_fallback;         /* 1: the whole input went through qe_csv_parse + qe_csv_pin */
+    int32_t reserved;
+    double h2d_ms;                 /* wall time of the text's copy to the device (file variant: read + copy) */
+    double kernel_ms;              /* wall time from the text on the device to the finished batch */
+} qe_csv_device_stats;
+int32_t qe_csv_device_last_stats(const qe_ctx *ctx, qe_csv_device_stats *out);
+/* 1 if the batch's column carries a validity bitmap (the plan of a query over it is specialised on that), 0 if not, -1 on
+ * a bad argument */
+int32_t qe_batch_column_nullable(const qe_batch *batch, int32_t col);
+/* a new handle on the dictionary of a STRING column (shared with the batch; free with qe_dict_free) */
+int32_t qe_batch_column_dict(const qe_batch *batch, int32_t col, qe_dict **out);
+
 /* ---- expressions ------------------------------------------------------------------ */
 /* compileExpression(expression, mode): evaluator/Compiler.kt:20-26 */
 int32_t qe_expr_compile(qe_ctx *ctx, const uint8_t *program, size_t len, qe_expr **out);

@@ -45,6 +45,8 @@ inline void set_bit(std::vector<uint64_t> &v, int64_t i) {
     v[(size_t)(i >> 6)] |= 1ull << (i & 63);
 }
 
+}  // namespace
+
 // java.lang.Double.parseDouble; returns false for what Java rejects
 bool java_parse_double(const char *p, size_t n, double &out) {
     while (n > 0 && (unsigned char)p[0] <= 0x20) { p++; n--; }
@@ -95,13 +97,16 @@ bool java_parse_double(const char *p, size_t n, double &out) {
     return ep && *ep == '\0';
 }
 
+namespace {
+
 bool kotlin_to_boolean(const char *p, size_t n) {
     return n == 4 && (p[0] | 0x20) == 't' && (p[1] | 0x20) == 'r' && (p[2] | 0x20) == 'u' && (p[3] | 0x20) == 'e';
 }
 
+}  // namespace
+
 // One record of the RFC 4180 dialect above.  `pos` advances past the record's line end.  Returns false at end of input
 // (no record).  `empty_line` is set for a completely empty line.
-struct Field { size_t begin, end; bool quoted; };
 bool next_record(const char *d, size_t n, size_t &pos, std::vector<Field> &fields, std::string &unq, std::vector<std::pair<size_t, size_t>> &unq_span,
                  bool &empty_line) {
     fields.clear();
@@ -147,7 +152,6 @@ bool next_record(const char *d, size_t n, size_t &pos, std::vector<Field> &field
     }
 }
 
-}  // namespace
 }  // namespace qe
 
 using namespace qe;

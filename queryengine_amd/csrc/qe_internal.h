@@ -50,6 +50,15 @@ int promote_type(int a, int b);
 const char *type_name(int t);
 const char *fn_name(int fn);
 
+// ---- CSV host parser (qe_csv.cpp), shared with the device parser (qe_csv_device.hip) ----------------------------------
+// java.lang.Double.parseDouble; false for what Java rejects
+bool java_parse_double(const char *p, size_t n, double &out);
+// one field of a record: [begin, end) of the text, or (quoted) begin = index into the unquoted spans
+struct Field { size_t begin, end; bool quoted; };
+// one record at `pos` (advanced past its line end); false at end of input; throws Error on a malformed quoted field
+bool next_record(const char *d, size_t n, size_t &pos, std::vector<Field> &fields, std::string &unq,
+                 std::vector<std::pair<size_t, size_t>> &unq_span, bool &empty_line);
+
 // ---- dictionaries ----------------------------------------------------------------------
 struct DictData {
     // process-wide serial number, assigned when the dictionary is created: plan caches key on it, never on the
@@ -404,6 +413,7 @@ struct qe_ctx {
     hipStream_t copy_stream = nullptr;
     qe::PinnedPool pinned;
     std::vector<struct qe_host_result *> host_results;   // alive host results (their copies may still read a qe_result)
+    qe_csv_device_stats csv_stats{};   // what the last qe_csv_parse*_device call did
 };
 
 struct qe_host_result {

@@ -17,12 +17,12 @@ from __future__ import annotations
 
 import csv
 import re
-from typing import Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
 from .datatypes import DataType, Field, Schema
-from .table import Column, ColumnarTable
+from .table import Column, ColumnarTable, Table
 
 _DEC = re.compile(r"^[+-]?(?:\d+\.?\d*(?:[eE][+-]?\d+)?|\.\d+(?:[eE][+-]?\d+)?)[dDfF]?$")
 _HEX = re.compile(r"^[+-]?0[xX](?:[0-9a-fA-F]+\.?[0-9a-fA-F]*|\.[0-9a-fA-F]+)[pP][+-]?\d+[dDfF]?$")
@@ -200,3 +200,127 @@ class CsvColumnarTable(ColumnarTable):
         t = read_csv_columns(path, schema)
         super().__init__(t.schema, t.columns)
         self.path = path
+
+
+class DeviceCsv:
+    """What ``read_csv_device`` returns: the device batch, the projected schema, the dictionaries of its STRING columns
+    (None for the others) and what the parse did (``qe_csv_device_last_stats``)."""
+
+    def __init__(self, batch, schema: Schema, dictionaries: List[Optional[List[str]]], stats: Dict[str, float]):
+        self.batch, self.schema, self.dictionaries, self.stats = batch, schema, dictionaries, stats
+
+    @property
+    def names(self) -> List[str]:
+        return [f.name for f in self.schema.fields]
+
+
+def read_csv_device(ctx, path_or_bytes, schema: Schema, projection: Optional[Sequence[str]] = None) -> DeviceCsv:
+    """CSV text -> an ``engine.DeviceBatch`` parsed on the GPU (qe_csv_parse_device / qe_csv_parse_file_device): the same
+    batch as ``read_csv_native(...).native.pin()``, or the same error.  Needs a device context."""
+    import ctypes as C
+    from . import engine as E
+    from . import native as N
+    names = list(projection) if projection is not None else [f.name for f in schema.fields]
+    fields = []
+    for name in names:
+        f = schema[name]
+        if f is None:
+            raise RuntimeError(f"projected field {name} not found in schema")          # CsvSourceOperator.kt:25-26
+        fields.append(f)
+    lib = N.lib()
+    cnames = (C.c_char_p * max(1, len(fields)))(*[f.name.encode("utf-8") for f in fields])
+    ctypes_ = (C.c_int32 * max(1, len(fields)))(*[int(f.type) for f in fields])
+    h = C.c_void_p()
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes)
+        st = lib.qe_csv_parse_device(ctx.handle, data, len(data), len(fields), cnames, ctypes_, C.byref(h))
+    else:
+        st = lib.qe_csv_parse_file_device(ctx.handle, str(path_or_bytes).encode("utf-8"), len(fields), cnames, ctypes_, C.byref(h))
+    if st != 0:
+        msg = (lib.qe_last_error(ctx.handle) or b"").decode("utf-8", "replace")
+        if "not found in csv headers" in msg:
+            raise RuntimeError(msg)
+        if "NumberFormatException" in msg:
+            raise NumberFormatException(msg)
+        raise N.QeError(st, msg)
+    batch = E.DeviceBatch(ctx, h)
+    dictionaries: List[Optional[List[str]]] = []
+    for j, f in enumerate(fields):
+        if f.type != DataType.STRING:
+            dictionaries.append(None)
+            continue
+        d = C.c_void_p()
+        N.check(ctx.handle, lib.qe_batch_column_dict(h, j, C.byref(d)))
+        try:
+            dictionaries.append([lib.qe_dict_entry(d, i).decode("utf-8") for i in range(lib.qe_dict_size(d))])
+        finally:
+            lib.qe_dict_free(ctx.handle, d)
+    s = N.CsvDeviceStats()
+    N.check(ctx.handle, lib.qe_csv_device_last_stats(ctx.handle, C.byref(s)))
+    stats = {k: getattr(s, k) for k, _ in N.CsvDeviceStats._fields_ if k != "reserved"}
+    return DeviceCsv(batch, Schema(fields), dictionaries, stats)
+
+
+class DeviceCsvTable(Table):
+    """A CSV table parsed on the GPU: its scan operator's ``device_batch(ctx)`` is the device-parsed batch of the projection,
+    parsed once per context and projection (like ``ColumnarScanOperator``).  ``query(...)`` over it returns the rows it
+    returns over ``CsvColumnarTable``."""
+
+    def __init__(self, path_or_bytes, schema: Schema):
+        self.source = path_or_bytes
+        self.schema = schema
+
+    def getScanOperator(self, projection: List[str]):
+        return DeviceCsvScanOperator(self, projection)
+
+
+class DeviceCsvScanOperator:
+    """Scan leaf over a DeviceCsvTable.  The GPU operators take ``device_batch(ctx)``; as a row source it materialises the
+    columns with ``qe_batch_column_to_host`` on the context of the last ``device_batch`` call."""
+
+    def __init__(self, table: DeviceCsvTable, projection: Sequence[str]):
+        self.table = table
+        self.projection = list(projection)
+        for name in self.projection:
+            if table.schema[name] is None:
+                raise ValueError(f"Unknown field {name}")
+        self._ctx = None
+        self._columns: Optional[List[Column]] = None
+        self._idx = 0
+
+    def _parsed(self, ctx) -> DeviceCsv:
+        cache = self.table.__dict__.setdefault("_device_batches", {})
+        for k in [k for k, v in cache.items() if v.batch.ctx.handle is None or v.batch.handle is None]:
+            del cache[k]
+        key = (id(ctx), tuple(self.projection))
+        p = cache.get(key)
+        if p is None or p.batch.ctx is not ctx or p.batch.handle is None or ctx.handle is None:
+            p = read_csv_device(ctx, self.table.source, self.table.schema, self.projection)
+            cache[key] = p
+        return p
+
+    def device_batch(self, ctx):
+        self._ctx = ctx
+        return self._parsed(ctx).batch
+
+    def columns(self) -> List[Column]:
+        if self._columns is None:
+            if self._ctx is None:
+                raise RuntimeError("DeviceCsvScanOperator: no device context yet (call device_batch(ctx) first)")
+            p = self._parsed(self._ctx)
+            self._columns = [p.batch.column_to_host(j, dictionary=p.dictionaries[j]) for j in range(len(self.projection))]
+        return self._columns
+
+    def open(self) -> None:
+        self._idx = 0
+
+    def close(self) -> None:
+        pass
+
+    def next(self) -> Optional[List[Any]]:
+        cols = self.columns()
+        i = self._idx
+        if not cols or i >= len(cols[0]):
+            return None
+        self._idx = i + 1
+        return [c.value(i) for c in cols]

@@ -58,6 +58,11 @@ class ColView(C.Structure):
                 ("count", C.c_int64), ("dict", C.c_void_p)]
 
 
+class CsvDeviceStats(C.Structure):
+    _fields_ = [("text_bytes", C.c_int64), ("nrows", C.c_int64), ("host_patched_fields", C.c_int64),
+                ("host_fallback", C.c_int32), ("reserved", C.c_int32), ("h2d_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
 # every symbol include/qe_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -92,6 +97,11 @@ SYMBOLS = [
     ("qe_csv_column", C.c_int32, [_P, C.c_int32, C.POINTER(ColDesc)]),
     ("qe_csv_pin", C.c_int32, [_P, _P, C.POINTER(_P)]),
     ("qe_csv_free", None, [_P, _P]),
+    ("qe_csv_parse_device", C.c_int32, [_P, C.c_char_p, C.c_size_t, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(_P)]),
+    ("qe_csv_parse_file_device", C.c_int32, [_P, C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(_P)]),
+    ("qe_csv_device_last_stats", C.c_int32, [_P, C.POINTER(CsvDeviceStats)]),
+    ("qe_batch_column_nullable", C.c_int32, [_P, C.c_int32]),
+    ("qe_batch_column_dict", C.c_int32, [_P, C.c_int32, C.POINTER(_P)]),
     ("qe_expr_compile", C.c_int32, [_P, C.c_char_p, C.c_size_t, C.POINTER(_P)]),
     ("qe_expr_result_type", C.c_int32, [_P]),
     ("qe_expr_free", None, [_P, _P]),

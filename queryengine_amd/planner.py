@@ -182,8 +182,8 @@ def default_context(mode: Mode, device: int = 0) -> E.Context:
 
 def _scan_of(tableRegistry: TableRegistry, node: LogicalScanNode) -> ColumnarScanOperator:
     op = tableRegistry.getTable(node.table).getScanOperator([f.name for f in node.schema.fields])   # Planner.kt:32
-    if not isinstance(op, ColumnarScanOperator):
-        raise TypeError("the GPU modes need a columnar scan leaf (ColumnarTable)")
+    if not isinstance(op, ColumnarScanOperator) and not callable(getattr(op, "device_batch", None)):
+        raise TypeError("the GPU modes need a columnar scan leaf (ColumnarTable) or a device-resident one (DeviceCsvTable)")
     return op
 
 
