@@ -253,8 +253,9 @@ int32_t qe_filter_project_prepare(qe_ctx *ctx, const qe_batch *batch, const qe_e
 /* GlobalAggregation(Projection(Filter(Scan))):
  * GlobalAggregationOperator.open (operator/GlobalAggregationOperator.kt:10-25) with
  * Accumulators.kt:26-107 semantics: nulls skipped, empty => null, COUNT => count.
- * SUM/AVG use a fixed-shape tree reduction (deterministic, not the reference's
- * sequential order: see DESIGN.md for the tolerance). */
+ * SUM/AVG use a fixed-shape tree reduction (deterministic: repeated executions, also on a
+ * fresh context, give the same bits; not the reference's sequential order: within
+ * gamma_c * sum|x| of the exact sum, see DESIGN.md 3.2 and tests/test_gpu_aggregate_numerics.py). */
 int32_t qe_filter_aggregate(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filter,
                             const qe_expr *const *exprs, const int32_t *agg_fns, int32_t nagg,
                             double *out_values, uint8_t *out_valid, int64_t *out_selected_rows);
@@ -267,7 +268,12 @@ int32_t qe_filter_aggregate(qe_ctx *ctx, const qe_batch *batch, const qe_expr *f
  * DOUBLE column): STRING (dictionary) / BOOLEAN keys with at most 2^20 combinations index a dense table; DOUBLE / INT64 /
  * INT32 keys (Double.equals: all NaNs one group, -0.0 and 0.0 two) and larger combinations are hashed.
  * SUM/AVG use native f64 atomics: exact when every partial sum is representable, otherwise order dependent in the last
- * bits. */
+ * bits: within gamma_c * sum|x| of the EXACT sum of a group's c valid values, gamma_c = c*u / (1 - c*u), u = 2^-53 (the
+ * bound of c terms added in any order; AVG: gamma_(c+1) * sum|x| / c, plus 2^-1075 for a quotient in the subnormal range),
+ * on every accumulation route -- pinned against math.fsum by tests/test_gpu_aggregate_numerics.py.  Decided special values: a group holding a NaN, or both infinities,
+ * sums to NaN; one infinity, to that infinity; only -0.0, to +0.0 (Accumulators.kt:40 starts from 0.0) while its MIN and
+ * MAX are -0.0; MIN/MAX let NaN win and order -0.0 below +0.0; all values NULL => NULL, COUNT 0.  Subnormal values are
+ * kept by the LDS and L2 f64 atomic adds (sums of multiples of 2^-1074 come out bit-exact). */
 int32_t qe_filter_groupby(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filter,
                           const qe_expr *const *keys, int32_t nkeys,
                           const qe_expr *const *exprs, const int32_t *agg_fns, int32_t nagg, qe_result **out);
