@@ -577,6 +577,26 @@ FusedGeometry geometry_of(const qe_ctx *ctx) {
     return g;
 }
 
+// The geometry steps of get_plan, in the order it calls them (later steps read what earlier ones set).  They settle in.geo
+// (and in.hp_lines) from plan->cg, which holds the generator's ANALYSIS of `in` here: no text is written before a compile.
+struct PlanGeometry {
+    qe_ctx *ctx;
+    CodegenInput &in;
+    Plan *plan;
+    const bool wide;
+    const int32_t *agg_fns;
+    void analyze() { plan->cg = analyze_fused_plan(in); }
+    void narrow_plan_wide_candidate();
+    void lds_table_1024_threads();
+    void hash_partitioned_tile();
+    void partitioned_tile_512_threads();
+    void hashed_unroll();
+    void dense_lds_tile();
+    void ring_lds_budget();
+    void register_estimate();
+    void compile_without_scratch();
+};
+
 std::shared_ptr<Plan> get_plan(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filter,
                                const qe_expr *const *projs, int32_t nproj, const int32_t *agg_fns, bool load,
                                const qe_expr *const *keys = nullptr, int32_t nkeys = 0, int geo_cand = 0, bool dense = false,
@@ -667,29 +687,55 @@ std::shared_ptr<Plan> get_plan(qe_ctx *ctx, const qe_batch *batch, const qe_expr
     auto it = ctx->plans.find(k);
     if (it != ctx->plans.end() && (it->second->kernel.fn || !load)) return it->second;
     auto plan = std::make_shared<Plan>();
-    plan->cg = generate_fused_source(in);
+    PlanGeometry pg{ctx, in, plan.get(), wide, agg_fns};
+    pg.analyze();
+    pg.narrow_plan_wide_candidate();
+    pg.lds_table_1024_threads();
+    pg.hash_partitioned_tile();
+    pg.partitioned_tile_512_threads();
+    pg.hashed_unroll();
+    pg.dense_lds_tile();
+    pg.ring_lds_budget();
+    if (ctx->opts.tuning[3] / 100 == 0) {
+        pg.register_estimate();
+        pg.compile_without_scratch();
+    } else {
+        plan->cg = generate_fused_source(in);
+    }
+    plan->geo = in.geo;
+    plan->explicit_geometry = ctx->opts.tuning[0] != 0 || ctx->opts.tuning[1] != 0 || ctx->opts.tuning[3] != 0 || ctx->opts.tuning[4] != 0 ||
+                              ctx->opts.tuning[7] != 0;
+    plan->aggregate = agg_fns != nullptr;
+    plan->kernel = ctx->jit->get(plan->cg.source, "qe_fused", load);
+    ctx->plans[k] = plan;
+    return plan;
+}
+
+void PlanGeometry::narrow_plan_wide_candidate() {
     if (wide && !in.dense && !agg_fns && in.group_keys.empty()) {
         // A plan that reads few bytes per row (cfg 4: a 4-byte code and an 8-byte value) pays the per-chunk work -- ticket,
         // descriptors, look-back -- on few bytes: its second candidate keeps the 16 load groups but hands out 32 Ki-row chunks
         // (16 sub-tiles) with the default rings instead of 8 Ki-row chunks.  Measured on cfg 4, 1 B rows: default 1.02 ms,
         // 16 groups x 4 sub-tiles 0.97 ms, 16 groups x 16 sub-tiles 0.80 ms.  The choice itself stays measured (best of 3).
         size_t inbytes = 0;
-        for (int c : plan->cg.used_cols) {
-            const int t = in.schema[(size_t)c].type;
-            inbytes += t == QE_BOOLEAN ? 0 : (t == QE_DOUBLE || t == QE_INT64) ? 8 : 4;
-        }
+        for (int c : plan->cg.used_cols) inbytes += (size_t)value_bytes(in.schema[(size_t)c].type);
         if (inbytes <= 16) {
             const FusedGeometry dflt = geometry_of(ctx);
             in.geo.subs_per_chunk = dflt.subs_per_chunk;
             in.geo.ring_entries = dflt.ring_entries;
-            plan->cg = generate_fused_source(in);
         }
     }
+}
+
+void PlanGeometry::lds_table_1024_threads() {
     if (!in.group_keys.empty() && !plan->cg.hashed && !plan->cg.table_in_lds && ctx->opts.tuning[0] == 0 &&
         (size_t)plan->cg.ngroups * plan->cg.table_words * 8 <= 144 * 1024) {
         in.geo.threads = 1024;   // the table fits ONE workgroup's LDS: 16 waves per CU share it (see table_in_lds)
-        plan->cg = generate_fused_source(in);
+        analyze();
     }
+}
+
+void PlanGeometry::hash_partitioned_tile() {
     if (plan->cg.hp && ctx->opts.tuning[1] == 0 && ctx->opts.tuning[0] == 0) {
         // the scatter pass sorts a workgroup tile's records in ONE LDS stage: 8 waves x 512 rows x 32-byte records = 128 KiB (one
         // workgroup per CU) was the fastest of the shapes measured on 100 000 DOUBLE keys, 512 partitions: 4 waves x 1024 rows
@@ -705,7 +751,7 @@ std::shared_ptr<Plan> get_plan(qe_ctx *ctx, const qe_batch *batch, const qe_expr
             // wide records (two or three per line) in many partitions: the lines' stage would force a smaller tile, i.e. shorter runs and
             // more padding than the {header, words} records have
             in.hp_lines = 0;
-            plan->cg = generate_fused_source(in);
+            analyze();
         }
         if (plan->cg.hp_line_recs) {
             while (u > 1 && lines_lds(u) > 156 * 1024) u /= 2;
@@ -714,42 +760,44 @@ std::shared_ptr<Plan> get_plan(qe_ctx *ctx, const qe_batch *batch, const qe_expr
             while (u > 1 && (size_t)(in.geo.threads / 64) * 128 * u * rec > 128 * 1024) u /= 2;
         }
         in.geo.unroll = u;
-        plan->cg = generate_fused_source(in);
     }
+}
+
+void PlanGeometry::partitioned_tile_512_threads() {
     if (plan->cg.partitioned && !plan->cg.hp && plan->cg.nparts > 128 && ctx->opts.tuning[0] == 0 && in.geo.threads == 256 &&
         8 + plan->cg.part_shift + 13 <= 32 && (size_t)8 * in.geo.sub_rows() * (1 + plan->cg.nvals) * 8 <= 128 * 1024) {
         // many partitions: a tile of 8 waves (8 Ki rows, one workgroup per CU) holds twice the records per partition, so the
         // whole-line padding of the scatter pass costs half as much (1 M keys: 45 % -> 22 % more records)
         in.geo.threads = 512;
-        plan->cg = generate_fused_source(in);
     }
+}
+
+void PlanGeometry::hashed_unroll() {
     if (plan->cg.hashed && ctx->opts.tuning[1] == 0 && in.geo.unroll > 4) {
         in.geo.unroll = 4;   // hashed group-by: the key words of 2 * U rows live in registers next to the inputs; it is bound by atomics, not by loads in flight
-        plan->cg = generate_fused_source(in);
     }
+}
+
+void PlanGeometry::dense_lds_tile() {
     if (in.dense) {
         // LDS budget of the parked tile: (waves * 128 * U) rows of every output column.  64 KiB lets two workgroups share a
         // CU (the second one streams while the first waits at its barriers); shrink the sub-tile, then the workgroup.
-        size_t rowbytes = 0;
-        for (const OutSpec &o : plan->cg.outs)
-            rowbytes += (o.type == QE_BOOLEAN ? 1 : (o.type == QE_DOUBLE || o.type == QE_INT64) ? 8 : 4) + (o.nullable ? 1 : 0);
-        rowbytes = std::max<size_t>(rowbytes, 1);
+        const size_t rowbytes = std::max<size_t>(output_row_bytes(plan->cg.outs), 1);
         auto tile_bytes = [&]() { return (size_t)(in.geo.threads / 64) * 128 * in.geo.unroll * rowbytes; };
         const size_t limit = 64 * 1024;
         while (tile_bytes() > limit && in.geo.unroll > 1 && ctx->opts.tuning[1] == 0) in.geo.unroll /= 2;
         while (tile_bytes() > limit && in.geo.threads > 128 && ctx->opts.tuning[0] == 0) in.geo.threads /= 2;
         if (tile_bytes() > 150 * 1024)
             fail(QE_ERR_UNSUPPORTED, "projection list too wide for the dense kernel's LDS tile (" + std::to_string(rowbytes) + " bytes per output row)");
-        plan->cg = generate_fused_source(in);
     }
+}
+
+void PlanGeometry::ring_lds_budget() {
     if (!agg_fns && in.filter && !in.dense) {
         // LDS budget of the per-wave FIFO of chunk buffers: waves * nbuf * ring * (bytes per output row).
         // Narrow rows get 3 buffers; wide rows 2 buffers and, if need be, fewer waves per workgroup so that a
         // workgroup stays within the 160 KiB of a CU (and several workgroups still fit).
-        size_t rowbytes = 0;
-        for (const OutSpec &o : plan->cg.outs)
-            rowbytes += (o.type == QE_BOOLEAN ? 1 : (o.type == QE_DOUBLE || o.type == QE_INT64) ? 8 : 4) + (o.nullable ? 1 : 0);
-        rowbytes = std::max<size_t>(rowbytes, 1);
+        const size_t rowbytes = std::max<size_t>(output_row_bytes(plan->cg.outs), 1);
         if (ctx->opts.tuning[7] / 100 == 0) in.geo.nbuf = 2;
         if (ctx->opts.tuning[0] == 0) {
             const size_t limit = 96 * 1024;
@@ -759,65 +807,61 @@ std::shared_ptr<Plan> get_plan(qe_ctx *ctx, const qe_batch *batch, const qe_expr
         if ((size_t)(in.geo.threads / 64) * in.geo.nbuf * in.geo.ring_entries * rowbytes > 156 * 1024)
             fail(QE_ERR_UNSUPPORTED, "projection list too wide for the fused kernel's LDS buffers (" + std::to_string(rowbytes) +
                                          " bytes per output row); use QE_EXEC_PER_NODE");
-        plan->cg = generate_fused_source(in);
     }
-    if (ctx->opts.tuning[3] / 100 == 0) {
-        // Register budget.  Per lane a sub-tile holds 2*U rows of every input column, later of every output
-        // column, plus one VGPR per boolean per row: shrink the sub-tile of very wide plans first.  Then ask
-        // for the highest occupancy (__launch_bounds__ waves per SIMD) that compiles WITHOUT SCRATCH: a spill
-        // turns into HBM traffic (84 B/lane of scratch cost 2.7 GB of extra writes per 1 B rows when measured).
-        auto dwords = [](int t) { return (t == QE_DOUBLE || t == QE_INT64) ? 2 : 1; };
-        for (;;) {
-            int in_dw = 0, out_dw = 0, nbool = 1, in_nulls = 0;
-            for (int c : plan->cg.used_cols) {
-                in_dw += dwords(in.schema[c].type);
-                in_nulls += in.schema[c].nullable ? 1 : 0;
-            }
-            for (const OutSpec &o : plan->cg.outs) {
-                out_dw += dwords(o.type);
-                nbool += o.nullable ? 1 : 0;
-            }
-            // the validity bits of ALL nullable inputs share one register per load group (qe_vb)
-            const int est = 2 * in.geo.unroll * (std::max(in_dw, out_dw) + nbool - 1) + (in_nulls ? in.geo.unroll : 0) + 54;
-            // three waves per SIMD need <= 168 VGPRs: a half-size sub-tile at 3 waves beat the full one at 2 waves
-            // (cfg 2 with nullable inputs: 4.47 vs 6.16 ms per 1 B rows)
-            plan->est_regs = est;
-            if (((est > 168 && in.geo.unroll > 4) || (est > 300 && in.geo.unroll > 2)) && ctx->opts.tuning[1] == 0 && !wide) {
-                in.geo.unroll /= 2;
-                if (!in.dense) in.geo.subs_per_chunk *= 2;   // keep the chunk size (the dense kernel's chunk IS the sub-tile)
-                plan->cg = generate_fused_source(in);
-                continue;
-            }
-            // (nullable cfg 2, est 122: 3 waves per SIMD 3.54 ms, 4 waves 3.69 ms -- the request also shapes the register allocation)
-            in.geo.min_waves = est <= 120 ? 4 : est <= 168 ? 3 : est <= 256 ? 2 : 1;
+}
+
+void PlanGeometry::register_estimate() {
+    // Register budget.  Per lane a sub-tile holds 2*U rows of every input column, later of every output
+    // column, plus one VGPR per boolean per row: shrink the sub-tile of very wide plans first.  Then ask
+    // for the highest occupancy (__launch_bounds__ waves per SIMD) that compiles WITHOUT SCRATCH: a spill
+    // turns into HBM traffic (84 B/lane of scratch cost 2.7 GB of extra writes per 1 B rows when measured).
+    auto dwords = [](int t) { return (t == QE_DOUBLE || t == QE_INT64) ? 2 : 1; };
+    for (;;) {
+        int in_dw = 0, out_dw = 0, nbool = 1, in_nulls = 0;
+        for (int c : plan->cg.used_cols) {
+            in_dw += dwords(in.schema[c].type);
+            in_nulls += in.schema[c].nullable ? 1 : 0;
+        }
+        for (const OutSpec &o : plan->cg.outs) {
+            out_dw += dwords(o.type);
+            nbool += o.nullable ? 1 : 0;
+        }
+        // the validity bits of ALL nullable inputs share one register per load group (qe_vb)
+        const int est = 2 * in.geo.unroll * (std::max(in_dw, out_dw) + nbool - 1) + (in_nulls ? in.geo.unroll : 0) + 54;
+        // three waves per SIMD need <= 168 VGPRs: a half-size sub-tile at 3 waves beat the full one at 2 waves
+        // (cfg 2 with nullable inputs: 4.47 vs 6.16 ms per 1 B rows)
+        plan->est_regs = est;
+        if (((est > 168 && in.geo.unroll > 4) || (est > 300 && in.geo.unroll > 2)) && ctx->opts.tuning[1] == 0 && !wide) {
+            in.geo.unroll /= 2;
+            if (!in.dense) in.geo.subs_per_chunk *= 2;   // keep the chunk size (the dense kernel's chunk IS the sub-tile)
+            continue;
+        }
+        // (nullable cfg 2, est 122: 3 waves per SIMD 3.54 ms, 4 waves 3.69 ms -- the request also shapes the register allocation)
+        in.geo.min_waves = est <= 120 ? 4 : est <= 168 ? 3 : est <= 256 ? 2 : 1;
+        break;
+    }
+}
+
+// compile (or hit the cache) at the estimated geometry; while the code object spills, ask for less and generate again
+void PlanGeometry::compile_without_scratch() {
+    for (;;) {
+        plan->cg = generate_fused_source(in);
+        plan->kernel = ctx->jit->get(plan->cg.source, "qe_fused", false);   // compile (or cache hit) only
+        if (ctx->jit->last_scratch <= 0) break;
+        const bool can_retry = in.geo.min_waves > 1 || (in.geo.unroll > 2 && ctx->opts.tuning[1] == 0);
+        if (can_retry) ctx->jit->reject(plan->cg.source, ctx->jit->last_scratch);   // superseded below: it does not stay in the cache
+        if (in.geo.min_waves > 2) {
+            in.geo.min_waves--;
+        } else if (in.geo.unroll > 2 && ctx->opts.tuning[1] == 0) {
+            in.geo.unroll /= 2;            // a smaller sub-tile rather than one wave per SIMD
+            if (!in.dense) in.geo.subs_per_chunk *= 2;
+            in.geo.min_waves = 3;
+        } else if (in.geo.min_waves > 1) {
+            in.geo.min_waves--;
+        } else {
             break;
         }
-        for (;;) {
-            plan->cg = generate_fused_source(in);
-            plan->kernel = ctx->jit->get(plan->cg.source, "qe_fused", false);   // compile (or cache hit) only
-            if (ctx->jit->last_scratch <= 0) break;
-            const bool can_retry = in.geo.min_waves > 1 || (in.geo.unroll > 2 && ctx->opts.tuning[1] == 0);
-            if (can_retry) ctx->jit->reject(plan->cg.source, ctx->jit->last_scratch);   // superseded below: it does not stay in the cache
-            if (in.geo.min_waves > 2) {
-                in.geo.min_waves--;
-            } else if (in.geo.unroll > 2 && ctx->opts.tuning[1] == 0) {
-                in.geo.unroll /= 2;            // a smaller sub-tile rather than one wave per SIMD
-                if (!in.dense) in.geo.subs_per_chunk *= 2;
-                in.geo.min_waves = 3;
-            } else if (in.geo.min_waves > 1) {
-                in.geo.min_waves--;
-            } else {
-                break;
-            }
-        }
     }
-    plan->geo = in.geo;
-    plan->explicit_geometry = ctx->opts.tuning[0] != 0 || ctx->opts.tuning[1] != 0 || ctx->opts.tuning[3] != 0 || ctx->opts.tuning[4] != 0 ||
-                              ctx->opts.tuning[7] != 0;
-    plan->aggregate = agg_fns != nullptr;
-    plan->kernel = ctx->jit->get(plan->cg.source, "qe_fused", load);
-    ctx->plans[k] = plan;
-    return plan;
 }
 
 int device_cus(int device) {

@@ -212,6 +212,15 @@ struct OutSpec {
     std::shared_ptr<DictData> dict;
 };
 
+// bytes per row of a column's values (BOOLEAN columns are bitmaps: 0)
+inline int value_bytes(int type) { return type == QE_BOOLEAN ? 0 : (type == QE_DOUBLE || type == QE_INT64) ? 8 : 4; }
+// bytes per output row while it waits in an LDS ring / tile or in staging: BOOLEAN values and validity are bytes there
+inline size_t output_row_bytes(const std::vector<OutSpec> &outs) {
+    size_t n = 0;
+    for (const OutSpec &o : outs) n += (o.type == QE_BOOLEAN ? 1 : value_bytes(o.type)) + (o.nullable ? 1 : 0);
+    return n;
+}
+
 struct FusedGeometry {
     int threads = 256;
     int rows_per_lane = 2;
@@ -301,6 +310,8 @@ struct CodegenOutput {
 };
 
 CodegenOutput generate_fused_source(const CodegenInput &in);
+// the same without `source`: the plan's metadata, no text is written (raises the same errors)
+CodegenOutput analyze_fused_plan(const CodegenInput &in);
 
 struct Kernel {
     hipModule_t module = nullptr;
