@@ -330,6 +330,24 @@ int32_t qe_result_concat(qe_ctx *ctx, const qe_result *const *parts, int32_t npa
  * the rows STABLY with Kotlin's compareValues -- NULL first, Double.compareTo (-0.0 < 0.0, NaN greatest), String.compareTo
  * (UTF-16 code units), false < true.  `column` is 0-based (the planner's ORDER BY <ordinal> is 1-based: Planner.kt:60). */
 int32_t qe_result_order_by(qe_ctx *ctx, const qe_result *result, int32_t column, qe_result **out);
+/* ORDER BY key[0], key[1], .. [LIMIT k]: the rows of `result` under the comparator key[0], then key[1], .., sorted STABLY
+ * (rows equal on every key keep their input order, in both directions).  An ascending key is the order above; a descending
+ * key is the reversed comparator (compareValues(b, a), what compareByDescending / thenByDescending use): NaN first, 0.0
+ * before -0.0, true before false, NULL LAST.  1 <= nkeys <= 8; a column may appear twice.  limit = k >= 0 returns exactly
+ * the first min(k, n) rows of that order (k = 0: an empty result with the schema of the input); limit < 0: every row.
+ * For 0 < k <= n / 2 the k-th smallest image of the first key is SELECTED on the device (8-bit radix select, the images are
+ * only read) and just the rows up to it, ties included, are sorted and gathered; when those are more than half of the rows
+ * (a boolean or few-valued first key) the full sort runs and is truncated -- the rows are the same either way.
+ * One ascending key without a limit returns the same bytes as qe_result_order_by.  The reference has one ascending key
+ * and no LIMIT (Query.g4:19); this is the Kotlin standard library's compareBy().thenByDescending() on a stable sortWith.
+ * QE_ERR_INVALID_ARG: null pointer, nkeys or a column out of range, a STRING key without dictionary; *out = NULL on error. */
+typedef struct { int32_t column; int32_t descending; } qe_sort_key;   /* column 0-based */
+int32_t qe_result_order_by_keys(qe_ctx *ctx, const qe_result *result, const qe_sort_key *keys, int32_t nkeys, int64_t limit,
+                                qe_result **out);
+/* what the last qe_result_order_by_keys (or qe_result_order_by: one ascending key, no limit) of this context did:
+ * out[0] path (0 full sort, 1 top-k selection), out[1] rows that went into the sort, out[2] radix passes run,
+ * out[3] selection passes run */
+int32_t qe_ctx_last_sort_stats(const qe_ctx *ctx, int64_t out[4]);
 
 /* ---- the exchange step of a row-range sharded scan -------------------------------------------------------
  * One process (one qe_ctx) per GPU; rank r scans rows [r*N/P, (r+1)*N/P) with NO communication.  Only a plan whose root

@@ -51,6 +51,9 @@ internal object QeNative {
     val qe_result_concat = handle("qe_result_concat", JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS)
     // ctx, result, column (0-based), qe_result** -> status: OrderByOperator.kt:9-15 on the device
     val qe_result_order_by = handle("qe_result_order_by", JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS)
+    // ctx, result, qe_sort_key[nkeys] {int column, int descending}, nkeys, limit (< 0: none), qe_result** -> status:
+    // compareBy().thenByDescending() on a stable sort, LIMIT as a top-k selection on the device
+    val qe_result_order_by_keys = handle("qe_result_order_by_keys", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_LONG, ADDRESS)
 
     // ---- the exchange step of a row-range sharded scan: one JVM process (one qe_ctx) per GPU ----
     // rank 0: qe_comm_unique_id(ctx, id128) -> the 128 bytes travel to the other ranks over the host's own channel

@@ -20,6 +20,7 @@
 
 #include "qe_internal.h"
 #include "qe_kernels.h"
+#include "qe_pernode_kernels.h"
 
 namespace qe {
 
@@ -236,6 +237,192 @@ static void need_dev(const qe_ctx *ctx) {
     QE_HIP(hipSetDevice(ctx->device));
 }
 
+// ORDER BY on the device: OrderByOperator.open (operator/OrderByOperator.kt:9-15) sorts the materialised rows stably
+// with compareValues -- null first, Double.compareTo (-0.0 < 0.0, NaN greatest), String.compareTo (UTF-16 code units),
+// false < true.  Key images + stable LSD radix sort of (key, row id) + gather of every column (qe_sort.hip).
+//
+// Several keys: the sort is stable, so it runs once per key from the LAST key to the first; the image of every key after
+// the first one sorted is taken through the permutation reached so far, so the scratch stays two (u64, u32) buffers.  A
+// descending key sorts the complement of its image and puts NULL last; ties keep their input order in both directions.
+//
+// LIMIT k (0 < k <= n / kTopkMaxShareDen; a larger k would make at least k rows candidates and goes straight to the full
+// sort, truncated): radix select of the k-th smallest image of the FIRST key (NULL is the smallest image ascending and
+// the greatest descending, so the NULL class is part of the order), the rows up to that threshold -- every tie of it
+// included -- are compacted in row order, and only these c candidates go through the multi-key sort.  The first k sorted
+// row ids are gathered.  When c exceeds n / kTopkMaxShareDen (a boolean or few-valued first key) the full sort runs instead.
+namespace {
+
+constexpr int64_t kTopkMaxShareDen = 2;       // candidates > n / 2: the full sort is taken (selection + the sort of c rows would cost as much)
+constexpr int64_t kTopkStopFloor = 16384;     // the selection stops once this few rows are left (sorting them costs no more than one pass)
+
+struct SortDriver {
+    qe_ctx *ctx;
+    Scratch &sc;
+    const qe_result *src;
+    const qe_sort_key *keys;
+    int32_t nkeys;
+    std::vector<const int *> d_ranks;   // per key: compareTo ranks of a STRING column's dictionary
+    std::vector<int> nranks;
+    std::vector<std::vector<std::vector<int32_t>>> h_ranks;   // the host tables, alive until the uploads have completed
+    unsigned long long *d_bits = nullptr;
+    int64_t radix_passes = 0;
+
+    void prepare() {
+        d_ranks.assign((size_t)nkeys, nullptr);
+        nranks.assign((size_t)nkeys, 0);
+        for (int32_t k = 0; k < nkeys; k++) {
+            const OutColumn &kc = src->cols[(size_t)keys[k].column];
+            if (kc.type != QE_STRING) continue;
+            if (!kc.dict) fail(QE_ERR_INVALID_ARG, "STRING column without dictionary");
+            // String.compareTo order of the dictionary (UTF-16 code units), as dense ranks
+            h_ranks.push_back(merged_ranks({&kc.dict->entries}));
+            const std::vector<int32_t> &ranks = h_ranks.back()[0];
+            int *d = (int *)sc.get(std::max<size_t>(ranks.size() * 4, 16));
+            if (!ranks.empty()) QE_HIP(hipMemcpyAsync(d, ranks.data(), ranks.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+            d_ranks[(size_t)k] = d;
+            nranks[(size_t)k] = (int)ranks.size();
+        }
+        if (!h_ranks.empty()) QE_HIP(hipStreamSynchronize(ctx->stream));
+        d_bits = (unsigned long long *)sc.get(16);
+    }
+
+    // images of key k for m elements: of rows 0..m-1 (perm == nullptr; rows_out[i] = i unless null) or of rows perm[0..m)
+    void images(int32_t k, int64_t m, const uint32_t *perm, unsigned long long *keys_out, uint32_t *rows_out) {
+        const OutColumn &kc = src->cols[(size_t)keys[k].column];
+        SortKeyArgs ka{};
+        ka.type = kc.type;
+        ka.data = kc.data;
+        ka.validity = (const unsigned long long *)kc.validity;
+        ka.ranks = d_ranks[(size_t)k];
+        ka.nranks = nranks[(size_t)k];
+        ka.n = m;
+        ka.keys = keys_out;
+        ka.rows = rows_out;
+        ka.perm = perm;
+        ka.descending = keys[k].descending ? 1 : 0;
+        launch_sort_keys(ctx->stream, ka);
+    }
+
+    // bits that differ between the m images (a digit without such a bit is the same in every key: its pass is skipped)
+    unsigned long long varying(const unsigned long long *k, int64_t m) {
+        const unsigned long long init[2] = {0ull, ~0ull};
+        QE_HIP(hipMemcpyAsync(d_bits, init, 16, hipMemcpyHostToDevice, ctx->stream));
+        launch_key_bits(ctx->stream, k, m, d_bits);
+        unsigned long long h_bits[2] = {0, 0};
+        QE_HIP(hipMemcpyAsync(h_bits, d_bits, 16, hipMemcpyDeviceToHost, ctx->stream));
+        QE_HIP(hipStreamSynchronize(ctx->stream));
+        return h_bits[0] & ~h_bits[1];
+    }
+
+    // stable sort of the m row ids in rbuf[0] (identity: they are 0..m-1 and are written here) by all keys; the index of
+    // the buffer that holds the sorted row ids is returned
+    int sort(int64_t m, bool identity, unsigned long long *kbuf[2], uint32_t *rbuf[2], uint32_t *hist) {
+        int cur = 0;
+        for (int32_t k = nkeys - 1; k >= 0; k--) {
+            const OutColumn &kc = src->cols[(size_t)keys[k].column];
+            const bool first_sorted = identity && k == nkeys - 1;
+            images(k, m, first_sorted ? nullptr : rbuf[cur], kbuf[cur], rbuf[cur]);
+            const unsigned long long var = varying(kbuf[cur], m);
+            for (int shift = 0; shift < 64; shift += 4) {
+                if (((var >> shift) & 15ull) == 0) continue;   // the same digit in every key
+                launch_radix_pass(ctx->stream, kbuf[cur], rbuf[cur], nullptr, m, shift, hist, kbuf[cur ^ 1], rbuf[cur ^ 1]);
+                cur ^= 1;
+                radix_passes++;
+            }
+            if (kc.validity) {   // NULL rows in front (compareValues) or, descending, behind; in their input order
+                launch_radix_pass(ctx->stream, kbuf[cur], rbuf[cur], kc.validity, m, keys[k].descending ? 65 : 64, hist, kbuf[cur ^ 1], rbuf[cur ^ 1]);
+                cur ^= 1;
+                radix_passes++;
+            }
+        }
+        return cur;
+    }
+};
+
+void order_by_impl(qe_ctx *ctx, const qe_result *src, const qe_sort_key *keys, int32_t nkeys, int64_t limit, const char *who, qe_result **out) {
+    need_dev(ctx);
+    const int64_t n = src->count;
+    if (n >= (1ll << 32)) fail(QE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 rows");
+    for (int32_t k = 0; k < nkeys; k++)
+        if (keys[k].column < 0 || keys[k].column >= (int32_t)src->cols.size()) fail(QE_ERR_INVALID_ARG, std::string(who) + ": key column out of range");
+    const int64_t nout = limit >= 0 && limit < n ? limit : n;
+    uint32_t any_validity = 0;
+    for (size_t c = 0; c < src->cols.size(); c++)
+        if (src->cols[c].validity) any_validity |= 1u << c;
+    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(make_output(ctx, src, nout, any_validity),
+                                                                      [ctx](qe_result *r) { free_output(ctx, r); });
+    int64_t stats[4] = {0, 0, 0, 0};
+    if (nout > 0) {
+        Scratch sc{ctx, {}};
+        SortDriver drv{ctx, sc, src, keys, nkeys};
+        drv.prepare();
+        unsigned long long *kbuf[2] = {nullptr, nullptr};
+        uint32_t *rbuf[2] = {nullptr, nullptr};
+        int64_t m = n;          // rows that go into the sort
+        bool identity = true;
+        if (nout < n && nout <= n / kTopkMaxShareDen) {
+            // ---- top-k: select on the first key's images, candidates in row order ----
+            unsigned long long *img = (unsigned long long *)sc.get((size_t)n * 8);
+            drv.images(0, n, nullptr, img, nullptr);
+            const unsigned long long var = drv.varying(img, n);
+            SelectState *st = (SelectState *)sc.get(sizeof(SelectState));
+            SelectState init{};
+            init.remaining = (unsigned long long)nout;
+            QE_HIP(hipMemcpyAsync(st, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
+            const unsigned long long stop_cap = (unsigned long long)std::max<int64_t>(nout + nout / 4, std::min<int64_t>(kTopkStopFloor, n / 16));
+            for (int shift = 56; shift >= 0; shift -= 8) {
+                if (((var >> shift) & 255ull) == 0) continue;   // the same digit in every key
+                launch_select_pass(ctx->stream, img, n, shift, st, stop_cap);
+            }
+            const int64_t nblocks = select_compact_blocks(n);
+            uint32_t *counts = (uint32_t *)sc.get((size_t)nblocks * 4), *offsets = (uint32_t *)sc.get((size_t)nblocks * 4);
+            uint32_t *sums = (uint32_t *)sc.get((size_t)((nblocks + 1023) / 1024) * 4);
+            unsigned long long *d_total = (unsigned long long *)sc.get(16);
+            launch_select_count(ctx->stream, img, n, st, counts);
+            pn::exclusive_scan_u32(ctx->stream, counts, offsets, sums, nblocks, d_total);
+            unsigned long long c = 0;
+            unsigned int passes = 0;
+            QE_HIP(hipMemcpyAsync(&c, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));   // the one read-back of the selection
+            QE_HIP(hipMemcpyAsync(&passes, &st->passes, 4, hipMemcpyDeviceToHost, ctx->stream));
+            QE_HIP(hipStreamSynchronize(ctx->stream));
+            if ((int64_t)c < nout || (int64_t)c > n) fail(QE_ERR_INTERNAL, std::string(who) + ": top-k selection kept " + std::to_string(c) + " of " +
+                                                                                std::to_string(n) + " rows for k = " + std::to_string(nout));
+            stats[3] = passes;
+            if ((int64_t)c <= n / kTopkMaxShareDen) {
+                m = (int64_t)c;
+                identity = false;
+                stats[0] = 1;
+                rbuf[0] = (uint32_t *)sc.get((size_t)m * 4);
+                launch_select_compact(ctx->stream, img, n, st, counts, offsets, rbuf[0], m);
+                kbuf[0] = (unsigned long long *)sc.get((size_t)m * 8);
+            } else {
+                kbuf[0] = img;   // too many candidates: the full sort, truncated
+            }
+        }
+        if (!kbuf[0]) kbuf[0] = (unsigned long long *)sc.get((size_t)m * 8);
+        kbuf[1] = (unsigned long long *)sc.get((size_t)m * 8);
+        if (!rbuf[0]) rbuf[0] = (uint32_t *)sc.get((size_t)m * 4);
+        rbuf[1] = (uint32_t *)sc.get((size_t)m * 4);
+        uint32_t *hist = (uint32_t *)sc.get((size_t)((m + 1023) / 1024) * 16 * 4);
+        const int cur = drv.sort(m, identity, kbuf, rbuf, hist);
+        stats[1] = m;
+        stats[2] = drv.radix_passes;
+        for (size_t c = 0; c < src->cols.size(); c++) {
+            const OutColumn &s_ = src->cols[c];
+            OutColumn &d_ = res->cols[c];
+            if (s_.type == QE_BOOLEAN) launch_gather_bits_rows(ctx->stream, (const uint64_t *)s_.data, rbuf[cur], nout, (uint64_t *)d_.data);
+            else launch_gather_rows(ctx->stream, (int)width_of(s_.type), s_.data, rbuf[cur], nout, d_.data);
+            if (d_.nullable) launch_gather_bits_rows(ctx->stream, s_.validity, rbuf[cur], nout, d_.validity);
+        }
+        QE_HIP(hipGetLastError());
+        QE_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    for (int i = 0; i < 4; i++) ctx->sort_stats[i] = stats[i];
+    *out = res.release();
+}
+
+}  // namespace
+
 extern "C" {
 
 int32_t qe_comm_unique_id(qe_ctx *ctx, qe_comm_id *out) {
@@ -332,75 +519,23 @@ int32_t qe_result_concat(qe_ctx *ctx, const qe_result *const *parts, int32_t npa
     });
 }
 
-// ORDER BY <column> on the device: OrderByOperator.open (operator/OrderByOperator.kt:9-15) sorts the materialised rows stably
-// with compareValues -- null first, Double.compareTo (-0.0 < 0.0, NaN greatest), String.compareTo (UTF-16 code units),
-// false < true.  Key images + stable LSD radix sort of (key, row id) + gather of every column (qe_sort.hip).
 int32_t qe_result_order_by(qe_ctx *ctx, const qe_result *src, int32_t column, qe_result **out) {
     if (!ctx || !src || !out || column < 0 || column >= (int32_t)src->cols.size()) return QE_ERR_INVALID_ARG;
     *out = nullptr;
-    return guarded_comm(ctx, [&] {
-        need_dev(ctx);
-        const int64_t n = src->count;
-        if (n >= (1ll << 32)) fail(QE_ERR_UNSUPPORTED, "qe_result_order_by: more than 2^32 rows");
-        uint32_t any_validity = 0;
-        for (size_t c = 0; c < src->cols.size(); c++)
-            if (src->cols[c].validity) any_validity |= 1u << c;
-        std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(make_output(ctx, src, n, any_validity),
-                                                                          [ctx](qe_result *r) { free_output(ctx, r); });
-        if (n > 0) {
-            Scratch sc{ctx, {}};
-            const OutColumn &kc = src->cols[(size_t)column];
-            unsigned long long *keys[2] = {(unsigned long long *)sc.get((size_t)n * 8), (unsigned long long *)sc.get((size_t)n * 8)};
-            uint32_t *rows[2] = {(uint32_t *)sc.get((size_t)n * 4), (uint32_t *)sc.get((size_t)n * 4)};
-            uint32_t *hist = (uint32_t *)sc.get((size_t)((n + 1023) / 1024) * 16 * 4);
-            SortKeyArgs ka{};
-            ka.type = kc.type;
-            ka.data = kc.data;
-            ka.validity = (const unsigned long long *)kc.validity;
-            ka.n = n;
-            ka.keys = keys[0];
-            ka.rows = rows[0];
-            if (kc.type == QE_STRING) {   // String.compareTo order of the dictionary (UTF-16 code units), as dense ranks
-                if (!kc.dict) fail(QE_ERR_INVALID_ARG, "STRING column without dictionary");
-                const std::vector<std::vector<int32_t>> ranks = merged_ranks({&kc.dict->entries});
-                int *d_ranks = (int *)sc.get(std::max<size_t>(ranks[0].size() * 4, 16));
-                if (!ranks[0].empty()) QE_HIP(hipMemcpyAsync(d_ranks, ranks[0].data(), ranks[0].size() * 4, hipMemcpyHostToDevice, ctx->stream));
-                QE_HIP(hipStreamSynchronize(ctx->stream));   // `ranks` is a host temporary
-                ka.ranks = d_ranks;
-                ka.nranks = (int)ranks[0].size();
-            }
-            launch_sort_keys(ctx->stream, ka);
-            // which digits differ at all?
-            unsigned long long *d_bits = (unsigned long long *)sc.get(16);
-            const unsigned long long init[2] = {0ull, ~0ull};
-            QE_HIP(hipMemcpyAsync(d_bits, init, 16, hipMemcpyHostToDevice, ctx->stream));
-            launch_key_bits(ctx->stream, keys[0], n, d_bits);
-            unsigned long long h_bits[2] = {0, 0};
-            QE_HIP(hipMemcpyAsync(h_bits, d_bits, 16, hipMemcpyDeviceToHost, ctx->stream));
-            QE_HIP(hipStreamSynchronize(ctx->stream));
-            const unsigned long long varying = h_bits[0] & ~h_bits[1];
-            int cur = 0;
-            for (int shift = 0; shift < 64; shift += 4) {
-                if (((varying >> shift) & 15ull) == 0) continue;   // the same digit in every key
-                launch_radix_pass(ctx->stream, keys[cur], rows[cur], nullptr, n, shift, hist, keys[cur ^ 1], rows[cur ^ 1]);
-                cur ^= 1;
-            }
-            if (kc.validity) {   // NULL rows in front (compareValues), in their input order
-                launch_radix_pass(ctx->stream, keys[cur], rows[cur], kc.validity, n, 64, hist, keys[cur ^ 1], rows[cur ^ 1]);
-                cur ^= 1;
-            }
-            for (size_t c = 0; c < src->cols.size(); c++) {
-                const OutColumn &s_ = src->cols[c];
-                OutColumn &d_ = res->cols[c];
-                if (s_.type == QE_BOOLEAN) launch_gather_bits_rows(ctx->stream, (const uint64_t *)s_.data, rows[cur], n, (uint64_t *)d_.data);
-                else launch_gather_rows(ctx->stream, (int)width_of(s_.type), s_.data, rows[cur], n, d_.data);
-                if (d_.nullable) launch_gather_bits_rows(ctx->stream, s_.validity, rows[cur], n, d_.validity);
-            }
-            QE_HIP(hipGetLastError());
-            QE_HIP(hipStreamSynchronize(ctx->stream));
-        }
-        *out = res.release();
-    });
+    const qe_sort_key key{column, 0};
+    return guarded_comm(ctx, [&] { order_by_impl(ctx, src, &key, 1, -1, "qe_result_order_by", out); });
+}
+
+int32_t qe_result_order_by_keys(qe_ctx *ctx, const qe_result *src, const qe_sort_key *keys, int32_t nkeys, int64_t limit, qe_result **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !src || !out || !keys || nkeys < 1 || nkeys > 8) return QE_ERR_INVALID_ARG;
+    return guarded_comm(ctx, [&] { order_by_impl(ctx, src, keys, nkeys, limit, "qe_result_order_by_keys", out); });
+}
+
+int32_t qe_ctx_last_sort_stats(const qe_ctx *ctx, int64_t out[4]) {
+    if (!ctx || !out) return QE_ERR_INVALID_ARG;
+    for (int i = 0; i < 4; i++) out[i] = ctx->sort_stats[i];
+    return QE_OK;
 }
 
 // Materialise a sharded result on rank `root`: *out is the concatenation in rank order there, NULL elsewhere.

@@ -425,6 +425,7 @@ struct qe_ctx {
     qe::PinnedPool pinned;
     std::vector<struct qe_host_result *> host_results;   // alive host results (their copies may still read a qe_result)
     qe_csv_device_stats csv_stats{};   // what the last qe_csv_parse*_device call did
+    int64_t sort_stats[4] = {0, 0, 0, 0};   // qe_ctx_last_sort_stats: path, rows sorted, radix passes, selection passes
 };
 
 struct qe_host_result {

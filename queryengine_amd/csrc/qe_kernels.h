@@ -63,15 +63,32 @@ struct SortKeyArgs {
     int nranks;
     long long n;
     unsigned long long *keys;
-    unsigned int *rows;
+    unsigned int *rows;             // rows[i] = i is written when `perm` is null (may be null: images only)
+    const unsigned int *perm;       // not null: keys[j] = image of row perm[j] (a later key of a multi-key sort)
+    int descending;                 // 1: the complement of the image (reversed comparator; NULL = all ones)
 };
 void launch_sort_keys(hipStream_t s, const SortKeyArgs &a);
 // or_and[0] |= every key, or_and[1] &= every key (caller initialises to {0, ~0})
 void launch_key_bits(hipStream_t s, const unsigned long long *keys, int64_t n, unsigned long long *or_and);
 // one stable LSD radix pass over the 4 key bits at `shift` (shift == 64: over the validity bit of each element's row, NULL
-// first); hist: 16 * ceil(n / 1024) u32 of scratch
+// first; shift == 65: NULL last, for a descending key); hist: 16 * ceil(n / 1024) u32 of scratch
 void launch_radix_pass(hipStream_t s, const unsigned long long *keys, const uint32_t *rows, const uint64_t *validity, int64_t n, int shift,
                        uint32_t *hist, unsigned long long *keys_out, uint32_t *rows_out);
+// ORDER BY .. LIMIT k: radix select over the first key's images (8 bits per pass, most significant first).  The state lives
+// in device memory and is zero-initialised by the caller except `remaining` = k; launch_select_pass = histogram of the digit
+// at `shift` among the rows that match the prefix + the one-wave step that extends the prefix (and sets `done` once at most
+// stop_cap rows are <= the prefix).  Candidates = rows whose masked image is <= the prefix, ties of the k-th row included.
+struct SelectState {
+    unsigned long long prefix, mask, remaining, below;
+    unsigned int bucket, done, passes, pad;
+    unsigned int hist[256];
+};
+void launch_select_pass(hipStream_t s, const unsigned long long *keys, int64_t n, int shift, SelectState *state, unsigned long long stop_cap);
+int64_t select_compact_blocks(int64_t n);   // blocks of the two kernels below = entries of counts / offsets
+void launch_select_count(hipStream_t s, const unsigned long long *keys, int64_t n, const SelectState *state, uint32_t *counts);
+// row ids of the candidates in row order; offsets = exclusive scan of counts; at most `capacity` ids are written
+void launch_select_compact(hipStream_t s, const unsigned long long *keys, int64_t n, const SelectState *state, const uint32_t *counts,
+                           const uint32_t *offsets, uint32_t *rows_out, int64_t capacity);
 void launch_gather_rows(hipStream_t s, int width, const void *src, const uint32_t *rows, int64_t n, void *out);
 void launch_gather_bits_rows(hipStream_t s, const uint64_t *src, const uint32_t *rows, int64_t n, uint64_t *out);
 

@@ -22,7 +22,8 @@ __device__ __forceinline__ bool bit_at(const u64 *bm, i64 i) { return (bm[i >> 6
 
 __global__ void __launch_bounds__(256) sort_key_kernel(const SortKeyArgs a) {
     const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < a.n; j += stride) {
+        const i64 i = a.perm ? (i64)a.perm[j] : j;   // a later key of a multi-key sort: the image of the row that stands at j now
         u64 k = 0;   // NULL: before every value (compareValues)
         if (!a.validity || bit_at(a.validity, i)) {
             switch (a.type) {
@@ -43,8 +44,10 @@ __global__ void __launch_bounds__(256) sort_key_kernel(const SortKeyArgs a) {
             default: k = bit_at((const u64 *)a.data, i) ? 1ull : 0ull; break;   // BOOLEAN bitmap
             }
         }   // (NULL rows keep key 0 and are moved in front by one last pass on the validity bit: launch_radix_pass with shift 64)
-        a.keys[i] = k;
-        a.rows[i] = (u32)i;
+        // descending: the complement reverses the unsigned order (NULL becomes the greatest image; the validity pass with
+        // shift 65 puts it behind every value, also behind a value whose image is all ones)
+        a.keys[j] = a.descending ? ~k : k;
+        if (!a.perm && a.rows) a.rows[j] = (u32)j;
     }
 }
 void launch_sort_keys(hipStream_t s, const SortKeyArgs &a) {
@@ -71,10 +74,11 @@ void launch_key_bits(hipStream_t s, const unsigned long long *keys, int64_t n, u
 // ---- one stable radix pass (4 bits): histogram per block of 1024 elements -> scan -> stable scatter ----------------------
 constexpr int kSortBlock = 1024;
 
-// digit of element i: 4 key bits at `shift`, or (shift == 64) the validity bit of its row: NULL (0) before everything else
+// digit of element i: 4 key bits at `shift`, or the validity bit of its row: (shift == 64) NULL (0) before everything else,
+// (shift == 65, a descending key) NULL (1) behind everything else
 __device__ __forceinline__ int sort_digit(const u64 *keys, const u32 *rows, const u64 *validity, i64 i, int shift) {
     if (shift < 64) return (int)((keys[i] >> shift) & 15ull);
-    return bit_at(validity, (i64)rows[i]) ? 1 : 0;
+    return (bit_at(validity, (i64)rows[i]) ? 1 : 0) ^ (shift & 1);
 }
 
 __global__ void __launch_bounds__(256) radix_hist_kernel(const u64 *keys, const u32 *rows, const u64 *validity, i64 n, int shift, u32 *hist, i64 nblocks) {
@@ -161,6 +165,164 @@ void launch_radix_pass(hipStream_t s, const unsigned long long *keys, const uint
     hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, s, hist, 16 * nblocks);
     hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, (const u64 *)keys, rows, (const u64 *)validity, (i64)n, shift,
                        (const u32 *)hist, nblocks, (u64 *)keys_out, rows_out);
+}
+
+// ---- ORDER BY .. LIMIT k: radix SELECT of the k-th smallest first-key image, then the candidates in row order -----------------
+// The images of the first key are only READ here (8 bytes per row and pass, nothing written per row), where a pass of the
+// sort reads and rewrites 12-byte pairs.  Most significant digit first, 8 bits per pass.  What has been found so far lives
+// in ONE SelectState in device memory: a pass reads it, the one-wave step kernel after it updates it; the host only queues
+// the kernels and never waits in between.
+//   prefix/mask : the digits found so far (mask = their bits; digits that are constant over all keys never enter it)
+//   remaining   : 1-based rank of the wanted row among the rows that match the prefix
+//   below       : rows whose processed digits are smaller than the prefix; below + bucket = rows <= the prefix = candidates
+//   done        : the candidate range is small enough (stop_cap): later passes return at once
+constexpr int kSelectCompactBlock = 4096;
+
+// Count one digit of a wave into the wave's own 256-bin LDS table.  Sorted and low-cardinality keys put the whole wave on
+// one bin, and same-address LDS atomics of a wave serialise: two rounds fold the lanes that share the digit of the first
+// active lane into one add (ballot + popcount); what is left after that is spread over other bins and adds itself.
+__device__ __forceinline__ void select_hist_add(u32 *h, bool active, int digit, int lane) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const u64 m = __ballot(active);
+        if (m == 0) return;   // wave-uniform
+        const int leader = __ffsll((long long)m) - 1;
+        const int d0 = __shfl(digit, leader, 64);
+        const u64 same = __ballot(active && digit == d0);
+        if (lane == leader) atomicAdd(&h[d0], (u32)__popcll(same));
+        if (digit == d0) active = false;
+    }
+    if (active) atomicAdd(&h[digit], 1u);
+}
+
+__global__ void __launch_bounds__(256) select_hist_kernel(const u64 *keys, i64 n, int shift, SelectState *st) {
+    __shared__ u32 s_h[4][256];   // one table per wave
+    if (st->done) return;         // uniform: the whole grid leaves
+    const u64 prefix = st->prefix, mask = st->mask;
+    for (int t = threadIdx.x; t < 4 * 256; t += 256) (&s_h[0][0])[t] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    u32 *h = s_h[threadIdx.x >> 6];
+    // two rows (16 bytes) per lane; the pair count is padded to whole waves so that every lane of a wave takes part in the ballots
+    const i64 npairs = (((n + 1) >> 1) + 63) & ~63ll;
+    const i64 stride = (i64)gridDim.x * 256;
+    for (i64 p = (i64)blockIdx.x * 256 + threadIdx.x; p < npairs; p += stride) {
+        const i64 i = 2 * p;
+        const bool in0 = i < n, in1 = i + 1 < n;
+        u64 k0 = 0, k1 = 0;
+        if (in1) {
+            const ulonglong2 v = *(const ulonglong2 *)(keys + i);
+            k0 = v.x;
+            k1 = v.y;
+        } else if (in0) {
+            k0 = keys[i];
+        }
+        select_hist_add(h, in0 && (k0 & mask) == prefix, (int)((k0 >> shift) & 255ull), lane);
+        select_hist_add(h, in1 && (k1 & mask) == prefix, (int)((k1 >> shift) & 255ull), lane);
+    }
+    __syncthreads();
+    const u32 c = s_h[0][threadIdx.x] + s_h[1][threadIdx.x] + s_h[2][threadIdx.x] + s_h[3][threadIdx.x];
+    if (c) atomicAdd(&st->hist[threadIdx.x], c);   // one global atomic per non-empty bin and workgroup
+}
+
+// ONE wave: the 256 counts -> the digit that holds the wanted rank, the rank inside it, and whether to stop
+__global__ void __launch_bounds__(64) select_step_kernel(SelectState *st, int shift, u64 stop_cap) {
+    if (st->done) return;
+    const int lane = threadIdx.x;
+    u32 c[4];
+    u32 sum = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        c[j] = st->hist[lane * 4 + j];
+        st->hist[lane * 4 + j] = 0;   // ready for the next pass
+        sum += c[j];
+    }
+    u64 incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 t = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    const u64 rem = st->remaining;
+    u64 cum = incl - sum;
+    if (cum < rem && rem <= incl) {   // exactly one lane (1 <= rem <= rows that match the prefix)
+        int j = 0;
+        while (j < 3 && rem > cum + c[j]) cum += c[j++];
+        st->prefix |= (u64)(lane * 4 + j) << shift;
+        st->mask |= 255ull << shift;
+        st->remaining = rem - cum;
+        st->below += cum;
+        st->bucket = c[j];
+        st->passes += 1;
+        if (st->below + c[j] <= stop_cap) st->done = 1;
+    }
+}
+
+__device__ __forceinline__ bool select_is_candidate(u64 k, u64 mask, u64 prefix) { return (k & mask) <= prefix; }
+
+// candidates per block of 4096 rows
+__global__ void __launch_bounds__(256) select_count_kernel(const u64 *keys, i64 n, const SelectState *st, u32 *counts) {
+    __shared__ u32 s_cnt[4];
+    const u64 prefix = st->prefix, mask = st->mask;
+    const i64 base = (i64)blockIdx.x * kSelectCompactBlock;
+    u32 cnt = 0;
+#pragma unroll
+    for (int r = 0; r < kSelectCompactBlock / 512; ++r) {
+        const i64 i = base + r * 512 + 2 * (i64)threadIdx.x;
+        if (i + 1 < n) {
+            const ulonglong2 v = *(const ulonglong2 *)(keys + i);
+            cnt += (select_is_candidate(v.x, mask, prefix) ? 1u : 0u) + (select_is_candidate(v.y, mask, prefix) ? 1u : 0u);
+        } else if (i < n) {
+            cnt += select_is_candidate(keys[i], mask, prefix) ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// row ids of the candidates, in row order: a block without candidates (nearly all of them for a small k) leaves at once
+__global__ void __launch_bounds__(256) select_compact_kernel(const u64 *keys, i64 n, const SelectState *st, const u32 *counts, const u32 *offsets,
+                                                             u32 *rows_out, i64 capacity) {
+    __shared__ u32 s_wave_cnt[4];
+    if (counts[blockIdx.x] == 0) return;   // uniform
+    const u64 prefix = st->prefix, mask = st->mask;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const i64 base = (i64)blockIdx.x * kSelectCompactBlock;
+    u32 running = offsets[blockIdx.x];
+    for (int r = 0; r < kSelectCompactBlock / 256; ++r) {
+        const i64 i = base + r * 256 + threadIdx.x;
+        const bool is = i < n && select_is_candidate(keys[i], mask, prefix);
+        const u64 m = __ballot(is);
+        const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
+        if (lane == 0) s_wave_cnt[wave] = (u32)__popcll(m);
+        __syncthreads();
+        u32 pos = running + rank;
+        for (int w = 0; w < wave; ++w) pos += s_wave_cnt[w];
+        if (is && (i64)pos < capacity) rows_out[pos] = (u32)i;
+        running += s_wave_cnt[0] + s_wave_cnt[1] + s_wave_cnt[2] + s_wave_cnt[3];
+        __syncthreads();
+    }
+}
+
+void launch_select_pass(hipStream_t s, const unsigned long long *keys, int64_t n, int shift, SelectState *state, unsigned long long stop_cap) {
+    if (n <= 0) return;
+    const i64 blocks = (n + 511) / 512;
+    hipLaunchKernelGGL(select_hist_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, (const u64 *)keys, (i64)n, shift, state);
+    hipLaunchKernelGGL(select_step_kernel, dim3(1), dim3(64), 0, s, state, shift, (u64)stop_cap);
+}
+int64_t select_compact_blocks(int64_t n) { return (n + kSelectCompactBlock - 1) / kSelectCompactBlock; }
+void launch_select_count(hipStream_t s, const unsigned long long *keys, int64_t n, const SelectState *state, uint32_t *counts) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(select_count_kernel, dim3((unsigned)select_compact_blocks(n)), dim3(256), 0, s, (const u64 *)keys, (i64)n, state, counts);
+}
+void launch_select_compact(hipStream_t s, const unsigned long long *keys, int64_t n, const SelectState *state, const uint32_t *counts,
+                           const uint32_t *offsets, uint32_t *rows_out, int64_t capacity) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(select_compact_kernel, dim3((unsigned)select_compact_blocks(n)), dim3(256), 0, s, (const u64 *)keys, (i64)n, state, counts, offsets,
+                       rows_out, (i64)capacity);
 }
 
 // ---- gather of one bitmap through the sorted row ids (value columns use the per-node gather) ---------------------------

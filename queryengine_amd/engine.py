@@ -148,6 +148,24 @@ class Context:
         N.check(self.handle, self._lib.qe_result_order_by(self.handle, result.handle, column, C.byref(h)))
         return Result(self, h)
 
+    def order_by_keys(self, result: "Result", keys: Sequence, limit: Optional[int] = None) -> "Result":
+        """qe_result_order_by_keys: the rows of `result` sorted stably by `keys` = [(column0, descending), ...] (a descending
+        key is the reversed comparator: NULL last); `limit` = k keeps the first min(k, n) rows of that order."""
+        keys = list(keys)
+        arr = (N.SortKey * max(1, len(keys)))(*[N.SortKey(int(c), 1 if d else 0) for c, d in keys])
+        h = C.c_void_p()
+        N.check(self.handle, self._lib.qe_result_order_by_keys(self.handle, result.handle, arr, len(keys),
+                                                               -1 if limit is None else int(limit), C.byref(h)))
+        return Result(self, h)
+
+    def last_sort_stats(self) -> dict:
+        """qe_ctx_last_sort_stats: what the last order_by / order_by_keys did -- path ("sort" or "select"), rows that went
+        into the sort, radix passes and selection passes run."""
+        out = (C.c_int64 * 4)()
+        N.check(self.handle, self._lib.qe_ctx_last_sort_stats(self.handle, out))
+        return {"path": "select" if out[0] == 1 else "sort", "sorted_rows": int(out[1]), "radix_passes": int(out[2]),
+                "select_passes": int(out[3])}
+
     def concat(self, parts: Sequence["Result"]) -> "Result":
         """qe_result_concat: results of this device, concatenated in the given order."""
         arr = (C.c_void_p * max(1, len(parts)))(*[p.handle for p in parts])

@@ -63,6 +63,11 @@ class CsvDeviceStats(C.Structure):
                 ("host_fallback", C.c_int32), ("reserved", C.c_int32), ("h2d_ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class SortKey(C.Structure):
+    """qe_sort_key: one ORDER BY key (column 0-based)."""
+    _fields_ = [("column", C.c_int32), ("descending", C.c_int32)]
+
+
 # every symbol include/qe_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -125,6 +130,8 @@ SYMBOLS = [
     ("qe_host_result_free", None, [_P, _P]),
     ("qe_result_concat", C.c_int32, [_P, C.POINTER(_P), C.c_int32, C.POINTER(_P)]),
     ("qe_result_order_by", C.c_int32, [_P, _P, C.c_int32, C.POINTER(_P)]),
+    ("qe_result_order_by_keys", C.c_int32, [_P, _P, _P, C.c_int32, C.c_int64, C.POINTER(_P)]),
+    ("qe_ctx_last_sort_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_comm_unique_id", C.c_int32, [_P, _P]),
     ("qe_comm_init", C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     ("qe_comm_rank", C.c_int32, [_P]),

@@ -81,11 +81,22 @@ class OrderByOperator(Operator):
 
     A consumer of the path's output.  When the source is a GPU operator whose result sits in HBM
     (``result()``), the rows are sorted there (qe_result_order_by: key images, stable radix sort, gather) and boxed
-    afterwards; any other source is drained and sorted on the host with the same ``compareValues`` order."""
+    afterwards; any other source is drained and sorted on the host with the same ``compareValues`` order.
 
-    def __init__(self, source: Operator, index: int):
+    ``keys`` = ``[(column0, descending), ...]`` orders by several columns (``compareBy().thenByDescending()`` on a stable
+    sort: a descending key is the reversed comparator, so NULL comes last; ties keep their input order) and ``limit``
+    keeps the first ``limit`` rows of that order.  On a GPU source that is qe_result_order_by_keys (top-k selection on
+    the device); on the host one stable ``list.sort`` per key from the last to the first."""
+
+    def __init__(self, source: Operator, index: int, keys: Optional[Sequence] = None, limit: Optional[int] = None):
         self.source = source
         self.index = index
+        self.keys = None if keys is None else tuple((int(c), bool(d)) for c, d in keys)
+        if self.keys is not None and not self.keys:
+            raise ValueError("OrderByOperator: keys must not be empty")
+        if limit is not None and limit < 0:
+            raise ValueError("OrderByOperator: limit must not be negative")
+        self.limit = limit
         self._iter = None
         self._sorted: Optional[E.Result] = None
 
@@ -94,7 +105,10 @@ class OrderByOperator(Operator):
             self.source.open()
             try:
                 res = self.source.result()
-                self._sorted = self.source.ctx.order_by(res, self.index)
+                if self.keys is None and self.limit is None:
+                    self._sorted = self.source.ctx.order_by(res, self.index)
+                else:
+                    self._sorted = self.source.ctx.order_by_keys(res, self.keys or [(self.index, False)], self.limit)
             finally:
                 self.source.close()
             cols = self._sorted.to_columns()
@@ -102,7 +116,11 @@ class OrderByOperator(Operator):
             self._iter = ([c.value(i) for c in cols] for i in range(n))
             return
         data = mapTo(self.source, [], lambda row: list(row))
-        data.sort(key=lambda row: _compare_key(row[self.index]))   # list.sort is stable, like java.util.List.sort
+        # list.sort is stable, like java.util.List.sort -- also under reverse=True, which keeps ties in input order
+        for column, descending in reversed(self.keys or ((self.index, False),)):
+            data.sort(key=lambda row: _compare_key(row[column]), reverse=descending)
+        if self.limit is not None:
+            data = data[:self.limit]
         self._iter = iter(data)
 
     def close(self) -> None:

@@ -61,9 +61,12 @@ class LogicalAggregationNode(LogicalNode):
 
 @dataclass(frozen=True)
 class LogicalOrderByNode(LogicalNode):
-    """evaluator/LogicalPlan.kt:12; ``index`` is the 1-based select position of ``ORDER BY n``."""
+    """evaluator/LogicalPlan.kt:12; ``index`` is the 1-based select position of ``ORDER BY n`` (of the first key).
+    ``keys`` = every key as (1-based ordinal, descending), empty = the single ascending key ``index``; ``limit`` = k."""
     source: LogicalNode
     index: int
+    keys: tuple = ()
+    limit: Optional[int] = None
 
 
 @dataclass(frozen=True)
@@ -150,7 +153,11 @@ def buildLogicalPlan(tableRegistry: TableRegistry, query: Query) -> LogicalNode:
     """Planner.kt:8-28 for the shapes of the hot path; ORDER BY wraps the finished plan (Planner.kt:13)."""
     if query.orderByColumn is not None:
         inner = buildLogicalPlan(tableRegistry, Query(query.select, query.from_, query.filter, None))
-        return LogicalOrderByNode(inner, query.orderByColumn)
+        keys = tuple(query.orderBy) or ((query.orderByColumn, False),)
+        for ordinal, _ in keys:
+            if not 1 <= ordinal <= len(query.select):
+                raise SchemaException(f"ORDER BY {ordinal} is not in the select list (1..{len(query.select)})")
+        return LogicalOrderByNode(inner, query.orderByColumn, keys, query.limit)
     schema = tableRegistry.getSchema(query.from_)
     resolver = _ResolveSchema(schema)
     # rewritePlan visits the Projection before its source (ResolveSchema.kt:24-33): SELECT list first, then WHERE
@@ -200,7 +207,11 @@ def buildPhysicalPlan(tableRegistry: TableRegistry, plan: LogicalNode, mode: Mod
     """Planner.kt:30-63 with the Filter/Projection(/global Aggregation) subtree fused into one GPU operator."""
     ctx = ctx or default_context(mode)
     if isinstance(plan, LogicalOrderByNode):     # Planner.kt:58-61
-        return OrderByOperator(buildPhysicalPlan(tableRegistry, plan.source, mode, ctx), plan.index - 1)
+        source = buildPhysicalPlan(tableRegistry, plan.source, mode, ctx)
+        keys = [(ordinal - 1, descending) for ordinal, descending in (plan.keys or ((plan.index, False),))]
+        if keys == [(plan.index - 1, False)] and plan.limit is None:
+            return OrderByOperator(source, plan.index - 1)     # the reference's form: qe_result_order_by
+        return OrderByOperator(source, plan.index - 1, keys, plan.limit)
     if isinstance(plan, LogicalProjectionNode):
         m = _match_filter_scan(plan.source)
         if m is not None:

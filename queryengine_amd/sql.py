@@ -34,7 +34,9 @@ class Query:
     select: tuple
     from_: str
     filter: Optional[Expression]
-    orderByColumn: Optional[int]
+    orderByColumn: Optional[int]          # the first ORDER BY ordinal (1-based), as in the reference
+    orderBy: tuple = ()                   # every ORDER BY key: (ordinal, descending)
+    limit: Optional[int] = None
 
 
 _TOKEN = re.compile(r"""
@@ -210,9 +212,25 @@ def parseQuery(text: str) -> Query:
     p.expect("kw", "FROM")
     from_ = p.identifier()
     flt = p.expression() if p.accept("kw", "WHERE") else None
-    order = None
+    # ORDER BY n [ASC|DESC] {, n [ASC|DESC]} [LIMIT k] (the reference has one ascending ordinal: Query.g4:19).  ASC, DESC
+    # and LIMIT are plain identifiers everywhere else: they are only looked for here.
+    def word(*names):
+        k, v = p.peek()
+        if k == "ident" and v.upper() in names:
+            p.take()
+            return v.upper()
+        return None
+
+    keys = []
+    limit = None
     if p.accept("kw", "ORDER"):
         p.expect("kw", "BY")
-        order = int(p.expect("integer"))
+        while True:
+            ordinal = int(p.expect("integer"))
+            keys.append((ordinal, word("ASC", "DESC") == "DESC"))
+            if not p.accept("op", ","):
+                break
+        if word("LIMIT"):
+            limit = int(p.expect("integer"))
     p.expect("eof")
-    return Query(tuple(select), from_, flt, order)
+    return Query(tuple(select), from_, flt, keys[0][0] if keys else None, tuple(keys), limit)
