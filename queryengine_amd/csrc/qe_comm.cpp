@@ -193,20 +193,8 @@ static void free_output(qe_ctx *ctx, qe_result *r) {
     delete r;
 }
 
-// scratch buffers that go back to the pool when the call ends
-struct Scratch {
-    qe_ctx *ctx;
-    std::vector<void *> bufs;
-    void *get(size_t bytes) {
-        void *p = ctx->pool.alloc(std::max<size_t>(bytes, 16));
-        bufs.push_back(p);
-        return p;
-    }
-    ~Scratch() { for (void *p : bufs) ctx->pool.release(p); }
-};
-
-static uint64_t *ones_bitmap(qe_ctx *ctx, Scratch &sc, int64_t n) {
-    uint64_t *p = (uint64_t *)sc.get(words_of(n) * 8);
+static uint64_t *ones_bitmap(qe_ctx *ctx, PoolScratch &sc, int64_t n) {
+    uint64_t *p = (uint64_t *)sc.alloc(words_of(n) * 8);
     QE_HIP(hipMemsetAsync(p, 0xff, words_of(n) * 8, ctx->stream));
     return p;
 }
@@ -257,7 +245,7 @@ constexpr int64_t kTopkStopFloor = 16384;     // the selection stops once this f
 
 struct SortDriver {
     qe_ctx *ctx;
-    Scratch &sc;
+    PoolScratch &sc;
     const qe_result *src;
     const qe_sort_key *keys;
     int32_t nkeys;
@@ -277,13 +265,13 @@ struct SortDriver {
             // String.compareTo order of the dictionary (UTF-16 code units), as dense ranks
             h_ranks.push_back(merged_ranks({&kc.dict->entries}));
             const std::vector<int32_t> &ranks = h_ranks.back()[0];
-            int *d = (int *)sc.get(std::max<size_t>(ranks.size() * 4, 16));
+            int *d = (int *)sc.alloc(std::max<size_t>(ranks.size() * 4, 16));
             if (!ranks.empty()) QE_HIP(hipMemcpyAsync(d, ranks.data(), ranks.size() * 4, hipMemcpyHostToDevice, ctx->stream));
             d_ranks[(size_t)k] = d;
             nranks[(size_t)k] = (int)ranks.size();
         }
         if (!h_ranks.empty()) QE_HIP(hipStreamSynchronize(ctx->stream));
-        d_bits = (unsigned long long *)sc.get(16);
+        d_bits = (unsigned long long *)sc.alloc(16);
     }
 
     // images of key k for m elements: of rows 0..m-1 (perm == nullptr; rows_out[i] = i unless null) or of rows perm[0..m)
@@ -353,7 +341,7 @@ void order_by_impl(qe_ctx *ctx, const qe_result *src, const qe_sort_key *keys, i
                                                                       [ctx](qe_result *r) { free_output(ctx, r); });
     int64_t stats[4] = {0, 0, 0, 0};
     if (nout > 0) {
-        Scratch sc{ctx, {}};
+        PoolScratch sc(ctx);
         SortDriver drv{ctx, sc, src, keys, nkeys};
         drv.prepare();
         unsigned long long *kbuf[2] = {nullptr, nullptr};
@@ -362,10 +350,10 @@ void order_by_impl(qe_ctx *ctx, const qe_result *src, const qe_sort_key *keys, i
         bool identity = true;
         if (nout < n && nout <= n / kTopkMaxShareDen) {
             // ---- top-k: select on the first key's images, candidates in row order ----
-            unsigned long long *img = (unsigned long long *)sc.get((size_t)n * 8);
+            unsigned long long *img = (unsigned long long *)sc.alloc((size_t)n * 8);
             drv.images(0, n, nullptr, img, nullptr);
             const unsigned long long var = drv.varying(img, n);
-            SelectState *st = (SelectState *)sc.get(sizeof(SelectState));
+            SelectState *st = (SelectState *)sc.alloc(sizeof(SelectState));
             SelectState init{};
             init.remaining = (unsigned long long)nout;
             QE_HIP(hipMemcpyAsync(st, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
@@ -375,9 +363,9 @@ void order_by_impl(qe_ctx *ctx, const qe_result *src, const qe_sort_key *keys, i
                 launch_select_pass(ctx->stream, img, n, shift, st, stop_cap);
             }
             const int64_t nblocks = select_compact_blocks(n);
-            uint32_t *counts = (uint32_t *)sc.get((size_t)nblocks * 4), *offsets = (uint32_t *)sc.get((size_t)nblocks * 4);
-            uint32_t *sums = (uint32_t *)sc.get((size_t)((nblocks + 1023) / 1024) * 4);
-            unsigned long long *d_total = (unsigned long long *)sc.get(16);
+            uint32_t *counts = (uint32_t *)sc.alloc((size_t)nblocks * 4), *offsets = (uint32_t *)sc.alloc((size_t)nblocks * 4);
+            uint32_t *sums = (uint32_t *)sc.alloc((size_t)((nblocks + 1023) / 1024) * 4);
+            unsigned long long *d_total = (unsigned long long *)sc.alloc(16);
             launch_select_count(ctx->stream, img, n, st, counts);
             pn::exclusive_scan_u32(ctx->stream, counts, offsets, sums, nblocks, d_total);
             unsigned long long c = 0;
@@ -392,18 +380,18 @@ void order_by_impl(qe_ctx *ctx, const qe_result *src, const qe_sort_key *keys, i
                 m = (int64_t)c;
                 identity = false;
                 stats[0] = 1;
-                rbuf[0] = (uint32_t *)sc.get((size_t)m * 4);
+                rbuf[0] = (uint32_t *)sc.alloc((size_t)m * 4);
                 launch_select_compact(ctx->stream, img, n, st, counts, offsets, rbuf[0], m);
-                kbuf[0] = (unsigned long long *)sc.get((size_t)m * 8);
+                kbuf[0] = (unsigned long long *)sc.alloc((size_t)m * 8);
             } else {
                 kbuf[0] = img;   // too many candidates: the full sort, truncated
             }
         }
-        if (!kbuf[0]) kbuf[0] = (unsigned long long *)sc.get((size_t)m * 8);
-        kbuf[1] = (unsigned long long *)sc.get((size_t)m * 8);
-        if (!rbuf[0]) rbuf[0] = (uint32_t *)sc.get((size_t)m * 4);
-        rbuf[1] = (uint32_t *)sc.get((size_t)m * 4);
-        uint32_t *hist = (uint32_t *)sc.get((size_t)((m + 1023) / 1024) * 16 * 4);
+        if (!kbuf[0]) kbuf[0] = (unsigned long long *)sc.alloc((size_t)m * 8);
+        kbuf[1] = (unsigned long long *)sc.alloc((size_t)m * 8);
+        if (!rbuf[0]) rbuf[0] = (uint32_t *)sc.alloc((size_t)m * 4);
+        rbuf[1] = (uint32_t *)sc.alloc((size_t)m * 4);
+        uint32_t *hist = (uint32_t *)sc.alloc((size_t)((m + 1023) / 1024) * 16 * 4);
         const int cur = drv.sort(m, identity, kbuf, rbuf, hist);
         stats[1] = m;
         stats[2] = drv.radix_passes;
@@ -463,9 +451,9 @@ int32_t qe_comm_allgather_host(qe_ctx *ctx, const void *send, size_t nbytes, voi
     return guarded_comm(ctx, [&] {
         need_dev(ctx);
         if (!ctx->comm) fail(QE_ERR_COMM, "qe_comm_allgather_host: no communicator (qe_comm_init)");
-        Scratch sc{ctx, {}};
+        PoolScratch sc(ctx);
         const size_t n = (size_t)ctx->comm_nranks;
-        char *d_send = (char *)sc.get(nbytes), *d_recv = (char *)sc.get(nbytes * n);
+        char *d_send = (char *)sc.alloc(nbytes), *d_recv = (char *)sc.alloc(nbytes * n);
         QE_HIP(hipMemcpyAsync(d_send, send, nbytes, hipMemcpyHostToDevice, ctx->stream));
         QE_NCCL(rccl().AllGather(d_send, d_recv, nbytes, kNcclUint8, ctx->comm, ctx->stream));
         QE_HIP(hipMemcpyAsync(recv, d_recv, nbytes * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -493,7 +481,7 @@ int32_t qe_result_concat(qe_ctx *ctx, const qe_result *const *parts, int32_t npa
             total += h.count;
             any_validity |= h.validity_mask;
         }
-        Scratch sc{ctx, {}};
+        PoolScratch sc(ctx);
         std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(make_output(ctx, parts[0], total, any_validity),
                                                                           [ctx](qe_result *r) { free_output(ctx, r); });
         int64_t off = 0;
@@ -559,14 +547,14 @@ int32_t qe_gather(qe_ctx *ctx, const qe_result *local, int32_t root, qe_result *
         // others do not wait for it
         const bool too_wide = local->cols.size() > (size_t)kGatherMaxCols;
         RcclApi &nc = rccl();
-        Scratch sc{ctx, {}};
+        PoolScratch sc(ctx);
         // (1) all-gather of the result headers: counts -> offsets; shapes and dictionaries are checked on every rank
         GatherHeader mine = header_of(local, true);
         if (too_wide) mine.ncols = -1;
         std::vector<GatherHeader> hdr((size_t)nranks);
         {
-            GatherHeader *d_mine = (GatherHeader *)sc.get(sizeof(GatherHeader));
-            GatherHeader *d_all = (GatherHeader *)sc.get(sizeof(GatherHeader) * (size_t)nranks);
+            GatherHeader *d_mine = (GatherHeader *)sc.alloc(sizeof(GatherHeader));
+            GatherHeader *d_all = (GatherHeader *)sc.alloc(sizeof(GatherHeader) * (size_t)nranks);
             QE_HIP(hipMemcpyAsync(d_mine, &mine, sizeof mine, hipMemcpyHostToDevice, ctx->stream));
             QE_NCCL(nc.AllGather(d_mine, d_all, sizeof(GatherHeader), kNcclUint8, ctx->comm, ctx->stream));
             QE_HIP(hipMemcpyAsync(hdr.data(), d_all, sizeof(GatherHeader) * (size_t)nranks, hipMemcpyDeviceToHost, ctx->stream));
@@ -616,8 +604,8 @@ int32_t qe_gather(qe_ctx *ctx, const qe_result *local, int32_t root, qe_result *
                     if (n == 0 || r == root) continue;
                     for (size_t c = 0; c < ncols; c++) {
                         OutColumn &dst = res->cols[c];
-                        if (dst.type == QE_BOOLEAN) staged.push_back({(uint64_t *)sc.get(words_of(n) * 8), offset[r], n, (uint64_t *)dst.data});
-                        if (dst.nullable) staged.push_back({(uint64_t *)sc.get(words_of(n) * 8), offset[r], n, dst.validity});
+                        if (dst.type == QE_BOOLEAN) staged.push_back({(uint64_t *)sc.alloc(words_of(n) * 8), offset[r], n, (uint64_t *)dst.data});
+                        if (dst.nullable) staged.push_back({(uint64_t *)sc.alloc(words_of(n) * 8), offset[r], n, dst.validity});
                     }
                 }
             }
@@ -630,8 +618,8 @@ int32_t qe_gather(qe_ctx *ctx, const qe_result *local, int32_t root, qe_result *
         }
         {
             std::vector<int32_t> status((size_t)nranks, 0);
-            int32_t *d_mine = (int32_t *)sc.get(sizeof(int32_t));
-            int32_t *d_all = (int32_t *)sc.get(sizeof(int32_t) * (size_t)nranks);
+            int32_t *d_mine = (int32_t *)sc.alloc(sizeof(int32_t));
+            int32_t *d_all = (int32_t *)sc.alloc(sizeof(int32_t) * (size_t)nranks);
             QE_HIP(hipMemcpyAsync(d_mine, &my_status, sizeof my_status, hipMemcpyHostToDevice, ctx->stream));
             QE_NCCL(nc.AllGather(d_mine, d_all, sizeof(int32_t), kNcclUint8, ctx->comm, ctx->stream));
             QE_HIP(hipMemcpyAsync(status.data(), d_all, sizeof(int32_t) * (size_t)nranks, hipMemcpyDeviceToHost, ctx->stream));
@@ -720,7 +708,7 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
         if (batch->schema_only) fail(QE_ERR_INVALID_ARG, "schema-only batch (qe_batch_describe) cannot be executed");
         const int K = std::max(1, std::min(nslices <= 0 ? 8 : nslices, kGatherMaxSlices));
         RcclApi &nc = rccl();
-        Scratch sc{ctx, {}};
+        PoolScratch sc(ctx);
         // (0) count pre-pass: kept rows of every slice of this shard
         int64_t slice_rows = 0;
         std::vector<int64_t> counts = qe_int_count_slices(ctx, batch, filter, projections, nproj, &slice_rows, K);
@@ -745,8 +733,8 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
         mine.h.count = n_me;
         std::vector<SliceHeader> hdr((size_t)nranks);
         {
-            SliceHeader *d_mine = (SliceHeader *)sc.get(sizeof(SliceHeader));
-            SliceHeader *d_all = (SliceHeader *)sc.get(sizeof(SliceHeader) * (size_t)nranks);
+            SliceHeader *d_mine = (SliceHeader *)sc.alloc(sizeof(SliceHeader));
+            SliceHeader *d_all = (SliceHeader *)sc.alloc(sizeof(SliceHeader) * (size_t)nranks);
             QE_HIP(hipMemcpyAsync(d_mine, &mine, sizeof mine, hipMemcpyHostToDevice, ctx->stream));
             QE_NCCL(nc.AllGather(d_mine, d_all, sizeof(SliceHeader), kNcclUint8, ctx->comm, ctx->stream));
             QE_HIP(hipMemcpyAsync(hdr.data(), d_all, sizeof(SliceHeader) * (size_t)nranks, hipMemcpyDeviceToHost, ctx->stream));
@@ -780,7 +768,7 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
         const uint64_t *ones = nullptr;   // validity words of a column that is nullable on another rank only
         try {
             if ((any_validity & ~mine.h.validity_mask) != 0 && n_me > 0) {
-                uint64_t *w = (uint64_t *)sc.get(words_of(slice_rows) * 8);
+                uint64_t *w = (uint64_t *)sc.alloc(words_of(slice_rows) * 8);
                 QE_HIP(hipMemsetAsync(w, 0xff, words_of(slice_rows) * 8, ctx->stream));
                 ones = w;
             }
@@ -794,8 +782,8 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
                         const int64_t n = hdr[r].count[k];
                         for (size_t c = 0; c < ncols; c++) {
                             OutColumn &dst = res->cols[c];
-                            if (dst.type == QE_BOOLEAN) staged[(size_t)k].push_back({(uint64_t *)sc.get(words_of(n) * 8), off, n, (uint64_t *)dst.data});
-                            if (dst.nullable) staged[(size_t)k].push_back({(uint64_t *)sc.get(words_of(n) * 8), off, n, dst.validity});
+                            if (dst.type == QE_BOOLEAN) staged[(size_t)k].push_back({(uint64_t *)sc.alloc(words_of(n) * 8), off, n, (uint64_t *)dst.data});
+                            if (dst.nullable) staged[(size_t)k].push_back({(uint64_t *)sc.alloc(words_of(n) * 8), off, n, dst.validity});
                         }
                     }
                 }
@@ -809,8 +797,8 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
         }
         {
             std::vector<int32_t> status((size_t)nranks, 0);
-            int32_t *d_mine = (int32_t *)sc.get(sizeof(int32_t));
-            int32_t *d_all = (int32_t *)sc.get(sizeof(int32_t) * (size_t)nranks);
+            int32_t *d_mine = (int32_t *)sc.alloc(sizeof(int32_t));
+            int32_t *d_all = (int32_t *)sc.alloc(sizeof(int32_t) * (size_t)nranks);
             QE_HIP(hipMemcpyAsync(d_mine, &my_status, sizeof my_status, hipMemcpyHostToDevice, ctx->stream));
             QE_NCCL(nc.AllGather(d_mine, d_all, sizeof(int32_t), kNcclUint8, ctx->comm, ctx->stream));
             QE_HIP(hipMemcpyAsync(status.data(), d_all, sizeof(int32_t) * (size_t)nranks, hipMemcpyDeviceToHost, ctx->stream));

@@ -28,7 +28,7 @@
 #include <cstdio>
 #include <thread>
 
-#include "qe_internal.h"
+#include "qe_exec.h"
 #include "qe_csv_number.h"
 
 using i64 = long long;
@@ -404,26 +404,15 @@ namespace {
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
-// device buffers of one call, returned to the context's pool on every exit
-struct Scratch {
-    qe_ctx *ctx;
-    std::vector<void *> bufs;
-    explicit Scratch(qe_ctx *c) : ctx(c) {}
-    template <typename T>
-    T *get(size_t n) {
-        void *p = ctx->pool.alloc(std::max<size_t>(n * sizeof(T), 16));
-        bufs.push_back(p);
-        return (T *)p;
-    }
-    void keep(void *p) { bufs.erase(std::remove(bufs.begin(), bufs.end(), p), bufs.end()); }
-    ~Scratch() { for (void *p : bufs) ctx->pool.release(p); }
-};
+// n elements of T among the device buffers of one call (PoolScratch returns them to the context's pool on every exit)
+template <typename T>
+T *dev_array(PoolScratch &S, size_t n) { return (T *)S.alloc(n * sizeof(T)); }
 
 // exclusive sum of a[0..n) in place; a must hold n + 1 elements, a[n] = 0 on entry: the total lands in a[n]
-void scan(qe_ctx *ctx, Scratch &S, i64 *a, i64 n) {
+void scan(qe_ctx *ctx, PoolScratch &S, i64 *a, i64 n) {
     const i64 m = n + 1;
     const unsigned nb = grid_of(m, kScanPer);
-    i64 *sums = S.get<i64>((size_t)nb + 1);
+    i64 *sums = dev_array<i64>(S, (size_t)nb + 1);
     hipLaunchKernelGGL(scan_local_kernel, dim3(nb), dim3(256), 0, ctx->stream, a, m, sums);
     if (nb > 1) {
         QE_HIP(hipMemsetAsync(sums + nb, 0, sizeof(i64), ctx->stream));
@@ -560,21 +549,26 @@ struct FileSource : TextSource {
     }
 };
 
+struct BatchDeleter {
+    qe_ctx *ctx;
+    void operator()(qe_batch *b) const { free_batch(ctx, b); }
+};
+
 // The device passes over the text in `dev` (n bytes, padded with zeros to whole tiles).  Throws FallBack.
-qe_batch *parse_on_device(qe_ctx *ctx, Scratch &S, const unsigned char *dev, i64 n, const Request &rq, const std::vector<int> &idx) {
+qe_batch *parse_on_device(qe_ctx *ctx, PoolScratch &S, const unsigned char *dev, i64 n, const Request &rq, const std::vector<int> &idx) {
     hipStream_t st = ctx->stream;
     const i64 ntiles = (n + kTile - 1) / kTile;
-    u32 *flags = S.get<u32>(4);
+    u32 *flags = dev_array<u32>(S, 4);
     QE_HIP(hipMemsetAsync(flags, 0, 16, st));
     i64 nrows = 0;
     i64 *rec_start = nullptr;
     if (ntiles > 0) {
-        i64 *tq = S.get<i64>((size_t)ntiles + 1);
+        i64 *tq = dev_array<i64>(S, (size_t)ntiles + 1);
         QE_HIP(hipMemsetAsync(tq + ntiles, 0, sizeof(i64), st));
         hipLaunchKernelGGL(quote_count_kernel, dim3(grid_of(ntiles, 4)), dim3(256), 0, st, dev, ntiles, tq);
         scan(ctx, S, tq, ntiles);
         if (read_back(ctx, tq + ntiles) & 1) throw FallBack{};   // an unterminated quote
-        i64 *tr = S.get<i64>((size_t)ntiles + 1);
+        i64 *tr = dev_array<i64>(S, (size_t)ntiles + 1);
         QE_HIP(hipMemsetAsync(tr + ntiles, 0, sizeof(i64), st));
         hipLaunchKernelGGL(records_kernel<false>, dim3(grid_of(ntiles, 4)), dim3(256), 0, st, dev, n, ntiles, (const i64 *)tq, tr,
                            (i64 *)nullptr, flags);
@@ -582,7 +576,7 @@ qe_batch *parse_on_device(qe_ctx *ctx, Scratch &S, const unsigned char *dev, i64
         nrows = read_back(ctx, tr + ntiles);
         if (read_back(ctx, flags) & F_QUOTE_RULE) throw FallBack{};
         if (nrows >= (i64)0x7FFFFFFF) throw FallBack{};   // row ids of the dictionary table are 32-bit
-        rec_start = S.get<i64>((size_t)nrows + 1);
+        rec_start = dev_array<i64>(S, (size_t)nrows + 1);
         hipLaunchKernelGGL(records_kernel<true>, dim3(grid_of(ntiles, 4)), dim3(256), 0, st, dev, n, ntiles, (const i64 *)tq, tr,
                            rec_start, flags);
     }
@@ -590,24 +584,22 @@ qe_batch *parse_on_device(qe_ctx *ctx, Scratch &S, const unsigned char *dev, i64
     i64 *begin = nullptr;
     u32 *lenesc = nullptr;
     if (nrows > 0 && ncols > 0) {
-        begin = S.get<i64>((size_t)ncols * nrows);
-        lenesc = S.get<u32>((size_t)ncols * nrows);
-        int *field_of = S.get<int>((size_t)ncols);
+        begin = dev_array<i64>(S, (size_t)ncols * nrows);
+        lenesc = dev_array<u32>(S, (size_t)ncols * nrows);
+        int *field_of = dev_array<int>(S, (size_t)ncols);
         QE_HIP(hipMemcpyAsync(field_of, idx.data(), sizeof(int) * ncols, hipMemcpyHostToDevice, st));
         SpanArgs a{dev, n, rec_start, nrows, field_of, ncols, *std::max_element(idx.begin(), idx.end()), begin, lenesc};
         hipLaunchKernelGGL(spans_kernel, dim3(grid_of(nrows, 256)), dim3(256), 0, st, a);
     }
     // the batch: column buffers sized like qe_batch_create's
-    std::unique_ptr<qe_batch> b(new qe_batch());
+    std::unique_ptr<qe_batch, BatchDeleter> b(new qe_batch(), BatchDeleter{ctx});   // its columns go back to the pool unless it is released
     b->nrows = nrows;
-    struct Owned { qe_ctx *c; qe_batch *b; bool armed = true; ~Owned() { if (armed) for (auto &col : b->cols) { c->pool.release(col.data); c->pool.release(col.validity); } } };
-    Owned owned{ctx, b.get()};
     const size_t words = (size_t)((nrows + 63) / 64);
-    u32 *any_null = S.get<u32>((size_t)std::max(ncols, 1));
+    u32 *any_null = dev_array<u32>(S, (size_t)std::max(ncols, 1));
     QE_HIP(hipMemsetAsync(any_null, 0, sizeof(u32) * std::max(ncols, 1), st));
-    u32 *patch_count = S.get<u32>(1);
+    u32 *patch_count = dev_array<u32>(S, 1);
     const u32 patch_cap = (u32)std::min<i64>(std::max<i64>(nrows, 1), 1 << 20);
-    i64 *patch_rows = S.get<i64>(patch_cap);
+    i64 *patch_rows = dev_array<i64>(S, patch_cap);
     std::vector<int> dict_cols;
     for (int k = 0; k < ncols; k++) {
         Column c;
@@ -645,8 +637,8 @@ qe_batch *parse_on_device(qe_ctx *ctx, Scratch &S, const unsigned char *dev, i64
                         QE_HIP(hipMemcpy(&txt[0], dev + fb[j], txt.size(), hipMemcpyDeviceToHost));
                         if (!java_parse_double(txt.data(), txt.size(), vals[j])) throw FallBack{};
                     }
-                    i64 *drows = S.get<i64>(np);
-                    double *dvals = S.get<double>(np);
+                    i64 *drows = dev_array<i64>(S, np);
+                    double *dvals = dev_array<double>(S, np);
                     QE_HIP(hipMemcpyAsync(drows, rows.data(), sizeof(i64) * np, hipMemcpyHostToDevice, st));
                     QE_HIP(hipMemcpyAsync(dvals, vals.data(), sizeof(double) * np, hipMemcpyHostToDevice, st));
                     hipLaunchKernelGGL(scatter_f64_kernel, dim3(grid_of(np, 256)), dim3(256), 0, st, (double *)c.data,
@@ -668,12 +660,12 @@ qe_batch *parse_on_device(qe_ctx *ctx, Scratch &S, const unsigned char *dev, i64
         a.nrows = nrows;
         a.begin = kb;
         a.lenesc = kl;
-        a.hash = S.get<u64>((size_t)nrows);
-        a.slots = S.get<u32>(cap);
-        a.first = S.get<u32>(cap);
+        a.hash = dev_array<u64>(S, (size_t)nrows);
+        a.slots = dev_array<u32>(S, cap);
+        a.first = dev_array<u32>(S, cap);
         a.mask = cap - 1;
-        a.row_slot = S.get<u32>((size_t)nrows);
-        a.rank = S.get<i64>((size_t)nrows + 1);
+        a.row_slot = dev_array<u32>(S, (size_t)nrows);
+        a.rank = dev_array<i64>(S, (size_t)nrows + 1);
         a.codes = (int *)c.data;
         a.validity = (u64 *)c.validity;
         a.any_null = any_null + k;
@@ -686,15 +678,15 @@ qe_batch *parse_on_device(qe_ctx *ctx, Scratch &S, const unsigned char *dev, i64
         hipLaunchKernelGGL(dict_first_kernel, g, dim3(256), 0, st, a);
         scan(ctx, S, a.rank, nrows);
         const i64 nd = read_back(ctx, a.rank + nrows);
-        a.dist_row = S.get<i64>((size_t)nd);
-        a.dist_len = S.get<i64>((size_t)nd + 1);
+        a.dist_row = dev_array<i64>(S, (size_t)nd);
+        a.dist_len = dev_array<i64>(S, (size_t)nd + 1);
         QE_HIP(hipMemsetAsync(a.dist_len + nd, 0, sizeof(i64), st));
         hipLaunchKernelGGL(dict_codes_kernel, g, dim3(256), 0, st, a);
         scan(ctx, S, a.dist_len, nd);
         std::vector<i64> off((size_t)nd + 1);
         QE_HIP(hipMemcpyAsync(off.data(), a.dist_len, sizeof(i64) * (nd + 1), hipMemcpyDeviceToHost, st));
         QE_HIP(hipStreamSynchronize(st));
-        a.packed = S.get<unsigned char>((size_t)off[(size_t)nd]);
+        a.packed = dev_array<unsigned char>(S, (size_t)off[(size_t)nd]);
         hipLaunchKernelGGL(dict_pack_kernel, dim3(grid_of(nd, 256)), dim3(256), 0, st, a, nd);
         std::string bytes((size_t)off[(size_t)nd], '\0');
         if (!bytes.empty())
@@ -720,7 +712,6 @@ qe_batch *parse_on_device(qe_ctx *ctx, Scratch &S, const unsigned char *dev, i64
             }
     }
     QE_HIP(hipStreamSynchronize(st));
-    owned.armed = false;
     return b.release();
 }
 
@@ -752,11 +743,11 @@ int32_t check_args(qe_ctx *ctx, int32_t nfields, const char *const *names, const
     return QE_OK;
 }
 
-unsigned char *alloc_text(qe_ctx *ctx, Scratch &S, size_t n) {
+unsigned char *alloc_text(qe_ctx *ctx, PoolScratch &S, size_t n) {
     const size_t padded = ((n + kTile - 1) / kTile) * kTile + 64;
     void *p = nullptr;
     try {
-        p = S.get<unsigned char>(padded);
+        p = dev_array<unsigned char>(S, padded);
     } catch (const Error &e) {
         fail(QE_ERR_OOM, "CSV text of " + std::to_string(n) + " bytes does not fit in free device memory (" + e.msg + ")");
     }
@@ -781,7 +772,7 @@ int32_t qe_csv_parse_device(qe_ctx *ctx, const char *data, size_t nbytes, int32_
         size_t body = 0;
         std::vector<int> idx;
         if (!resolve_header(data, nbytes, rq, body, idx)) { fallback = true; return; }
-        Scratch S(ctx);
+        PoolScratch S(ctx);
         const size_t n = nbytes - body;
         auto t0 = Clock::now();
         unsigned char *dev = alloc_text(ctx, S, n);
@@ -835,7 +826,7 @@ int32_t qe_csv_parse_file_device(qe_ctx *ctx, const char *path, int32_t nfields,
             fallback = true;
             return;
         }
-        Scratch S(ctx);
+        PoolScratch S(ctx);
         const size_t n = nbytes - body;
         auto t0 = Clock::now();
         unsigned char *dev = alloc_text(ctx, S, n);

@@ -1,0 +1,1006 @@
+// qe_groupby.cpp -- the aggregating executors behind the C ABI: the global aggregate (qe_filter_aggregate) and GROUP BY
+// (qe_filter_groupby): run_groupby picks the route -- dense table, hashed table, dense ids or hash partitions.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <functional>
+
+#include "qe_exec.h"
+#include "qe_kernels.h"
+
+using namespace qe;
+
+namespace {
+
+constexpr int kScatterWgsPerCu = 2;   // workgroups per CU of the partitioned group-by's scatter pass
+
+qe_result *run_groupby_dense(qe_ctx *ctx, const qe_batch *batch, const std::shared_ptr<Plan> &plan, const int32_t *agg_fns, int32_t nagg);
+
+// GroupByAggregation over arbitrary key tuples (a DOUBLE / INT64 / INT32 key, or more key combinations than a dense table
+// holds): the hashed form.  Global open-addressing table, grown (x8) and the kernel run again when it got more than half
+// full; the used entries are collected on the device, sorted by smallest row id on the host (LinkedHashMap insertion order,
+// GroupByAggregationOperator.kt:22) and finished like the dense form's (Accumulators.kt:26-107).
+// Key columns of a hashed group-by result: row j's {null bits, key words..} come from `key_of(j)`.
+template <typename KeyOf>
+void append_key_columns(qe_ctx *ctx, const CodegenOutput &cg, qe_result *res, int64_t m, KeyOf key_of,
+                        std::vector<std::vector<unsigned long long>> &keep64, std::vector<std::vector<int32_t>> &keep32) {
+    const int NK = (int)cg.keys.size();
+    const size_t words = (size_t)std::max<int64_t>(1, (m + 63) / 64);
+    auto upload = [&](const void *src, size_t bytes) -> void * {
+        void *d = ctx->pool.alloc(std::max<size_t>(bytes, 16));
+        if (bytes) QE_HIP(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return d;
+    };
+    for (int k = 0; k < NK; k++) {
+        OutColumn oc;
+        oc.type = cg.keys[k].type;
+        oc.dict = cg.keys[k].dict;
+        oc.dict_handle.d = oc.dict;
+        std::vector<unsigned long long> valid(words, 0), vals64((size_t)std::max<int64_t>(m, 1), 0), bits(words, 0);
+        std::vector<int32_t> vals32((size_t)std::max<int64_t>(m, 1), 0);
+        bool any_null = false;
+        for (int64_t j = 0; j < m; j++) {
+            const unsigned long long *e = key_of(j);   // {null bits, key words..}
+            if ((e[0] >> k) & 1ull) { any_null = true; continue; }
+            valid[j >> 6] |= 1ull << (j & 63);
+            const unsigned long long kw = e[1 + k];
+            vals64[j] = kw;                       // DOUBLE: the canonical bits ARE the value; INT64: the value
+            vals32[j] = (int32_t)(int64_t)kw;     // INT32 / dictionary codes
+            if (kw) bits[j >> 6] |= 1ull << (j & 63);
+        }
+        oc.nullable = any_null;
+        if (oc.type == QE_BOOLEAN) {
+            keep64.push_back(bits);
+            oc.data = upload(keep64.back().data(), words * 8);
+        } else if (oc.type == QE_DOUBLE || oc.type == QE_INT64) {
+            keep64.push_back(vals64);
+            oc.data = upload(keep64.back().data(), (size_t)m * 8);
+        } else {
+            keep32.push_back(vals32);
+            oc.data = upload(keep32.back().data(), (size_t)m * 4);
+        }
+        if (any_null) {
+            keep64.push_back(valid);
+            oc.validity = (uint64_t *)upload(keep64.back().data(), words * 8);
+        }
+        res->cols.push_back(oc);
+    }
+}
+
+// Hashed group-by whose keys do not fit the LDS table: (1) qe_ht_build gives every key a dense id (global open-addressing
+// table, a 64 KiB id cache per workgroup; after its first rows a key is only READ) and writes the id of every kept row;
+// (2) the dense group-by -- LDS-privatised table or the partitioned passes -- runs on the id column; (3) the ids of the result
+// rows are turned back into key values.  nullptr: more keys than a dense table takes (the caller keeps the global-atomic form).
+qe_result *run_groupby_ids(qe_ctx *ctx, const qe_batch *batch, const Plan &plan, const qe_expr *filter, const qe_expr *const *exprs,
+                           const int32_t *agg_fns, int32_t nagg, bool *many_keys) {
+    const CodegenOutput &cg = plan.cg;
+    const int NK = (int)cg.keys.size(), BW = NK == 1 ? 2 : 3 + NK;   // single-key plans: 16-byte entries {key, state | null bits | id}
+    const int64_t n = batch->nrows;
+    PoolScratch temps(ctx);
+    auto talloc = [&](size_t bytes) { return temps.alloc(std::max<size_t>(bytes, 16)); };
+    uint32_t *d_ids = (uint32_t *)talloc((size_t)n * 4);
+    hipFunction_t f_build = nullptr;
+    QE_HIP(hipModuleGetFunction(&f_build, plan.kernel.module, "qe_ht_build"));
+    int64_t C = plan.id_capacity > 0 ? plan.id_capacity : (1ll << 16);
+    int64_t D = 0;
+    unsigned long long *d_keys = nullptr;
+    double build_ms = 0.0;
+    for (;;) {
+        unsigned long long *d_tab = (unsigned long long *)talloc((size_t)C * BW * 8);
+        d_keys = (unsigned long long *)talloc((size_t)C * (1 + NK) * 8);
+        QE_HIP(hipMemsetAsync(d_tab, 0, (size_t)C * BW * 8, ctx->stream));
+        QE_HIP(hipMemsetAsync(ctx->d_ctrl, 0, 96, ctx->stream));
+        const int64_t sub_rows = plan.geo.sub_rows();
+        const int64_t ntiles = (n + sub_rows - 1) / sub_rows;
+        const int waves = plan.geo.threads / 64;
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + waves - 1) / waves, (int64_t)device_cus(ctx->device) * 4));
+        FusedParams p;
+        fill_inputs(p, batch, plan);
+        p.agg_partial = (double *)d_tab;
+        p.capacity = C;
+        p.ticket = ctx->d_ctrl;
+        p.error = ctx->d_ctrl + 1;
+        p.desc = d_keys;
+        p.blk = (unsigned long long *)d_ids;
+        void *args[] = {&p};
+        if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+        QE_HIP(hipModuleLaunchKernel(f_build, grid, 1, 1, plan.geo.threads, 1, 1, 0, ctx->stream, args, nullptr));
+        if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        QE_HIP(hipMemcpyAsync(ctx->h_ctrl, ctx->d_ctrl, 32, hipMemcpyDeviceToHost, ctx->stream));
+        QE_HIP(hipStreamSynchronize(ctx->stream));
+        if (ctx->opts.profile) {
+            float ms = 0.f;
+            QE_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+            build_ms += ms;
+        }
+        const unsigned int *hc = (const unsigned int *)ctx->h_ctrl;
+        if (hc[1] != 0) {   // more than half full: a bigger table, again (the launch stopped at once: an attempt costs little)
+            if (many_keys && plan.id_capacity <= 0) {   // the first table of a plan that knows nothing yet: the caller takes over
+                *many_keys = true;
+                return nullptr;
+            }
+            if (C >= (1ll << 22)) return nullptr;
+            C *= 4;
+            continue;
+        }
+        D = hc[0];
+        break;
+    }
+    plan.id_capacity = C;
+    if (D > (1ll << 20) - 1) return nullptr;   // a dense table takes 2^20 groups (the id domain + its NULL code)
+    // (2) the dense group-by over [the batch's columns.., ids]: the id column is a dictionary-coded key whose dictionary is a
+    // placeholder of 2^k entries (only its size matters: the domain of the group id)
+    int64_t dom = 2;
+    while (dom < D) dom *= 2;
+    dom = std::min<int64_t>(dom, (1ll << 20) - 1);
+    std::shared_ptr<DictData> &idd = ctx->id_dicts[dom];
+    if (!idd) {
+        idd = std::make_shared<DictData>();
+        idd->entries.resize((size_t)dom);
+    }
+    qe_batch tmp;
+    tmp.nrows = n;
+    tmp.cols = batch->cols;
+    for (Column &c : tmp.cols) c.owned = false;
+    Column idc;
+    idc.type = QE_STRING;
+    idc.data = d_ids;
+    idc.validity = nullptr;
+    idc.dict = idd;
+    idc.owned = false;
+    tmp.cols.push_back(idc);
+    qe_expr kx;
+    {
+        Node nd;
+        nd.kind = N_COLUMN;
+        nd.type = QE_STRING;
+        nd.col = (int)batch->cols.size();
+        kx.e.nodes.push_back(nd);
+        kx.e.root = 0;
+        kx.e.max_stack = 1;
+        const char tag[] = "\xEEid-column";
+        kx.e.program.assign(tag, tag + sizeof tag - 1);
+        kx.e.program.push_back((uint8_t)batch->cols.size());
+    }
+    const qe_expr *kp[1] = {&kx};
+    auto dplan = get_plan(ctx, &tmp, PlanRequest{filter, exprs, nagg, agg_fns, kp, 1});
+    if (dplan->cg.hashed) fail(QE_ERR_INTERNAL, "dense-id plan came out hashed");
+    std::unique_ptr<qe_result, std::function<void(qe_result *)>> r(run_groupby_dense(ctx, &tmp, dplan, agg_fns, nagg),
+                                                                   [ctx](qe_result *q) { free_result(ctx, q); });
+    if (ctx->opts.profile) {   // one step = build pass + dense passes
+        ctx->last_ms += build_ms;
+        ctx->total_ms += build_ms;
+    }
+    // (3) ids of the result rows (column 0, in insertion order) -> key values
+    const int64_t m = r->count;
+    std::vector<int32_t> rid((size_t)std::max<int64_t>(m, 1));
+    std::vector<unsigned long long> hkeys((size_t)std::max<int64_t>(D, 1) * (1 + NK));
+    if (m > 0) QE_HIP(hipMemcpyAsync(rid.data(), r->cols[0].data, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (D > 0) QE_HIP(hipMemcpyAsync(hkeys.data(), d_keys, (size_t)D * (1 + NK) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    QE_HIP(hipStreamSynchronize(ctx->stream));
+    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [ctx](qe_result *q) { free_result(ctx, q); });
+    res->count = m;
+    res->capacity = m;
+    std::vector<std::vector<unsigned long long>> keep64;
+    std::vector<std::vector<int32_t>> keep32;
+    append_key_columns(ctx, cg, res.get(), m, [&](int64_t j) { return &hkeys[(size_t)rid[(size_t)j] * (1 + NK)]; }, keep64, keep32);
+    for (size_t c = 1; c < r->cols.size(); c++) {   // the aggregates move over as they are
+        res->cols.push_back(r->cols[c]);
+        r->cols[c].data = nullptr;
+        r->cols[c].validity = nullptr;
+    }
+    QE_HIP(hipStreamSynchronize(ctx->stream));
+    return res.release();
+}
+
+// The same on the device, for results of many groups (1 M groups cost the host ~70 ms and crossed the link twice): the entries are
+// ordered by first row (their keys = the first rows, a stable LSD radix sort over as many 4-bit digits as the batch's row ids
+// have), then one kernel writes every result column -- key values, finished accumulators, validity bitmaps -- in that order.  The
+// host only learns which columns hold a NULL anywhere (a column without one carries no bitmap, as the host path decides).
+qe_result *finish_hashed_groups_on_device(qe_ctx *ctx, const CodegenOutput &cg, const unsigned long long *d_entries, int64_t m, int64_t nrows,
+                                          const int32_t *agg_fns, int32_t nagg) {
+    const int W = cg.hash_words, NK = (int)cg.keys.size();
+    PoolScratch temps(ctx);
+    auto talloc = [&](size_t bytes) { return temps.alloc(std::max<size_t>(bytes, 16)); };
+    unsigned long long *keys[2] = {(unsigned long long *)talloc((size_t)m * 8), (unsigned long long *)talloc((size_t)m * 8)};
+    uint32_t *rows[2] = {(uint32_t *)talloc((size_t)m * 4), (uint32_t *)talloc((size_t)m * 4)};
+    uint32_t *hist = (uint32_t *)talloc((size_t)16 * (size_t)((m + 1023) / 1024) * 4);
+    launch_group_sort_keys(ctx->stream, d_entries, W, 2 + NK, m, keys[0], rows[0]);
+    int bits = 1;
+    while (bits < 62 && (1ll << bits) < nrows) bits++;
+    int cur = 0;
+    for (int shift = 0; shift < bits; shift += 4) {
+        launch_radix_pass(ctx->stream, keys[cur], rows[cur], nullptr, m, shift, hist, keys[1 - cur], rows[1 - cur]);
+        cur = 1 - cur;
+    }
+    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [ctx](qe_result *r) { free_result(ctx, r); });
+    res->count = m;
+    res->capacity = m;
+    const size_t words = (size_t)std::max<int64_t>(1, (m + 63) / 64);
+    GroupFinishArgs a{};
+    a.entries = d_entries;
+    a.rows = rows[cur];
+    a.m = m;
+    a.words = W;
+    a.nkeys = NK;
+    a.nagg = nagg;
+    unsigned int *d_flags = (unsigned int *)talloc(64);
+    QE_HIP(hipMemsetAsync(d_flags, 0, 64, ctx->stream));
+    a.flags = d_flags;
+    for (int k = 0; k < NK; k++) {
+        OutColumn oc;
+        oc.type = cg.keys[k].type;
+        oc.dict = cg.keys[k].dict;
+        oc.dict_handle.d = oc.dict;
+        const size_t bytes = oc.type == QE_BOOLEAN ? words * 8 : (oc.type == QE_DOUBLE || oc.type == QE_INT64) ? (size_t)m * 8 : (size_t)m * 4;
+        oc.data = ctx->pool.alloc(std::max<size_t>(bytes, 16));
+        oc.validity = (uint64_t *)ctx->pool.alloc(words * 8);
+        res->cols.push_back(oc);
+        a.key_type[k] = oc.type;
+        a.key_data[k] = oc.data;
+        a.key_valid[k] = (unsigned long long *)oc.validity;
+    }
+    for (int i = 0; i < nagg; i++) {
+        OutColumn oc;
+        oc.type = QE_DOUBLE;
+        oc.data = ctx->pool.alloc(std::max<size_t>((size_t)m * 8, 16));
+        oc.validity = (uint64_t *)ctx->pool.alloc(words * 8);
+        res->cols.push_back(oc);
+        a.agg_fn[i] = agg_fns[i];
+        a.cnt_src[i] = cg.cnt_src[(size_t)i];
+        a.agg_data[i] = (double *)oc.data;
+        a.agg_valid[i] = (unsigned long long *)oc.validity;
+    }
+    launch_group_finish(ctx->stream, a);
+    unsigned int flags[16] = {};
+    QE_HIP(hipMemcpyAsync(flags, d_flags, 64, hipMemcpyDeviceToHost, ctx->stream));
+    QE_HIP(hipGetLastError());
+    QE_HIP(hipStreamSynchronize(ctx->stream));
+    for (int c = 0; c < NK + nagg; c++) {   // a column without a NULL carries no bitmap
+        OutColumn &oc = res->cols[(size_t)c];
+        oc.nullable = flags[c < NK ? c : 4 + (c - NK)] != 0;
+        if (!oc.nullable) {
+            ctx->pool.release(oc.validity);
+            oc.validity = nullptr;
+        }
+    }
+    return res.release();
+}
+
+// The groups of a hashed GROUP BY, finished on the host: `dense` holds m entries of cg.hash_words words {state, null bits, key
+// words.., first row, (count, acc)..}.  Insertion order = ascending first row (LinkedHashMap, GroupByAggregationOperator.kt:22);
+// accumulators finish as Accumulators.kt:26-107 says.
+qe_result *finish_hashed_groups(qe_ctx *ctx, const CodegenOutput &cg, const unsigned long long *dense, int64_t m,
+                                const int32_t *agg_fns, int32_t nagg) {
+    const int W = cg.hash_words, NK = (int)cg.keys.size(), ACC = 2 + NK;
+    std::vector<std::pair<unsigned long long, int64_t>> order;
+    order.reserve((size_t)m);
+    for (int64_t g = 0; g < m; g++) order.emplace_back(dense[(size_t)g * W + ACC], g);
+    if (m < 4096) {
+        std::sort(order.begin(), order.end());
+    } else {
+        // first rows are distinct row ids < 2^42: three stable passes of a 14-bit radix sort (std::sort took ~80 of the 125 ms the
+        // host spent finishing 1 M groups)
+        std::vector<std::pair<unsigned long long, int64_t>> tmp(order.size());
+        std::vector<size_t> cnt((size_t)1 << 14);
+        unsigned long long all = 0;
+        for (const auto &o : order) all |= o.first;
+        for (int pass = 0; pass < 5 && (all >> (14 * pass)) != 0; pass++) {
+            const int sh = 14 * pass;
+            std::fill(cnt.begin(), cnt.end(), 0);
+            for (const auto &o : order) cnt[(size_t)((o.first >> sh) & 0x3fffull)]++;
+            size_t run = 0;
+            for (size_t &c : cnt) { const size_t t = c; c = run; run += t; }
+            for (const auto &o : order) tmp[cnt[(size_t)((o.first >> sh) & 0x3fffull)]++] = o;
+            order.swap(tmp);
+        }
+    }
+    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [ctx](qe_result *r) { free_result(ctx, r); });
+    res->count = m;
+    res->capacity = m;
+    const size_t words = (size_t)std::max<int64_t>(1, (m + 63) / 64);
+    auto upload = [&](const void *src, size_t bytes) -> void * {
+        void *d = ctx->pool.alloc(std::max<size_t>(bytes, 16));
+        if (bytes) QE_HIP(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return d;
+    };
+    std::vector<std::vector<unsigned long long>> keep64;   // host staging must outlive the async copies
+    std::vector<std::vector<int32_t>> keep32;
+    append_key_columns(ctx, cg, res.get(), m, [&](int64_t j) { return &dense[(size_t)order[(size_t)j].second * W + 1]; }, keep64, keep32);
+    std::vector<std::vector<double>> keep_vals;
+    for (int i = 0; i < nagg; i++) {
+        OutColumn oc;
+        oc.type = QE_DOUBLE;
+        std::vector<double> vals((size_t)std::max<int64_t>(m, 1), 0.0);
+        std::vector<unsigned long long> valid(words, 0);
+        bool any_null = false;
+        for (int64_t j = 0; j < m; j++) {
+            const unsigned long long *e = &dense[(size_t)order[j].second * W] + ACC;   // {first row, (count, acc)..}
+            const unsigned long long cnt = e[1 + 2 * cg.cnt_src[i]];
+            const unsigned long long raw = e[2 + 2 * i];
+            double v = 0.0;
+            bool ok = true;
+            switch (agg_fns[i]) {
+            case QE_AGG_COUNT: v = (double)cnt; break;                       // Accumulators.kt:26-36
+            case QE_AGG_SUM: std::memcpy(&v, &raw, 8); ok = cnt != 0; break;  // :47-53 empty => null
+            case QE_AGG_AVG: std::memcpy(&v, &raw, 8); ok = cnt != 0; if (ok) v /= (double)cnt; break;
+            default: {                                                        // MIN / MAX: undo the ordered key
+                long long key = (long long)raw;
+                long long b = key ^ ((key >> 63) & 0x7fffffffffffffffll);
+                std::memcpy(&v, &b, 8);
+                ok = cnt != 0;
+            }
+            }
+            if (ok) valid[j >> 6] |= 1ull << (j & 63);
+            else { any_null = true; v = 0.0; }
+            vals[j] = v;
+        }
+        oc.nullable = any_null;
+        keep_vals.push_back(std::move(vals));
+        oc.data = upload(keep_vals.back().data(), (size_t)m * 8);
+        if (any_null) {
+            keep64.push_back(std::move(valid));
+            oc.validity = (uint64_t *)upload(keep64.back().data(), words * 8);
+        }
+        res->cols.push_back(oc);
+    }
+    QE_HIP(hipStreamSynchronize(ctx->stream));
+    return res.release();
+}
+
+// `many_keys` (optional): set -- and nullptr returned, nothing decided for the plan -- when the id build's FIRST table fills up
+// (more than 32 768 keys): the caller has a better form for that many keys than a grown id table.
+qe_result *run_groupby_hashed(qe_ctx *ctx, const qe_batch *batch, const Plan &plan, const qe_expr *filter, const qe_expr *const *exprs,
+                              const int32_t *agg_fns, int32_t nagg, bool *many_keys) {
+    const CodegenOutput &cg = plan.cg;
+    const bool ids_allowed = !debug_bit(ctx, kDbgHashedGlobalAtomics) && batch->nrows < (1ll << 32);
+    bool ids_failed = plan.ids_overflow;   // more keys than a dense table takes, found out by an earlier execution: straight to the global-atomic form
+    if (plan.use_ids && ids_allowed && !ids_failed) {
+        qe_result *r = run_groupby_ids(ctx, batch, plan, filter, exprs, agg_fns, nagg, many_keys);
+        if (r) return r;
+        if (many_keys && *many_keys) return nullptr;
+        plan.ids_overflow = ids_failed = true;
+        plan.use_ids = false;
+    }
+    const int W = cg.hash_words, NK = (int)cg.keys.size(), ACC = 2 + NK;
+    if (W > 40) fail(QE_ERR_UNSUPPORTED, "too many GROUP BY keys + aggregates for one hash entry");
+    const int64_t n = batch->nrows;
+    HtInit init{};
+    init.words = W;
+    for (int w = 0; w < W; w++) init.word[w] = 0;
+    init.word[ACC] = ~0ull;   // smallest row id
+    for (int i = 0; i < nagg; i++)
+        init.word[ACC + 2 + 2 * i] = agg_fns[i] == QE_AGG_MIN ? 0x7fffffffffffffffull : agg_fns[i] == QE_AGG_MAX ? 0x8000000000000000ull : 0ull;
+    std::vector<unsigned long long> dense;
+    int64_t m = 0;
+    if (n > 0) {
+        int64_t C = plan.hash_capacity > 0 ? plan.hash_capacity : (1ll << 16);
+        for (;;) {
+            PoolScratch tab_scratch(ctx);
+            unsigned long long *d_tab = (unsigned long long *)tab_scratch.alloc((size_t)C * W * 8);
+            launch_ht_init(ctx->stream, d_tab, C, init);
+            QE_HIP(hipMemsetAsync(ctx->d_ctrl, 0, 96, ctx->stream));   // [0] entries in use (p.ticket), [1] error (p.error)
+            const int64_t sub_rows = plan.geo.sub_rows();
+            const int64_t ntiles = (n + sub_rows - 1) / sub_rows;
+            const int waves = plan.geo.threads / 64;
+            const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + waves - 1) / waves, (int64_t)device_cus(ctx->device) * 4));
+            FusedParams p;
+            fill_inputs(p, batch, plan);
+            p.agg_partial = (double *)d_tab;
+            p.capacity = C;
+            p.ticket = ctx->d_ctrl;
+            p.error = ctx->d_ctrl + 1;
+            p.stagger_chunks = ids_allowed && !ids_failed ? 1 : 0;   // a key that finds no room in LDS stops the launch (error 4) instead of going global
+            launch_fused(ctx, plan, p, grid);
+            QE_HIP(hipMemcpyAsync(ctx->h_ctrl, ctx->d_ctrl, 16, hipMemcpyDeviceToHost, ctx->stream));
+            QE_HIP(hipStreamSynchronize(ctx->stream));
+            const unsigned int *hc = (const unsigned int *)ctx->h_ctrl;
+            if (hc[1] == 4) {   // the keys do not fit the LDS table: dense ids from now on (this execution included)
+                plan.use_ids = true;
+                qe_result *r = run_groupby_ids(ctx, batch, plan, filter, exprs, agg_fns, nagg, many_keys);
+                if (r) return r;
+                if (many_keys && *many_keys) return nullptr;
+                ids_failed = true;   // more keys than a dense table takes: the global-atomic form after all -- and remembered,
+                plan.ids_overflow = true;   // so that later executions do not run the failing id build again
+                plan.use_ids = false;
+                continue;
+            }
+            collect_time(ctx);
+            if (hc[1] != 0) {   // more than half full (or a probe sequence ran out): a bigger table, again
+                if (C >= (1ll << 28)) fail(QE_ERR_UNSUPPORTED, "GROUP BY produced more than 2^27 groups");
+                C *= 8;
+                continue;
+            }
+            plan.hash_capacity = C;
+            const int64_t used = hc[0];
+            // more than a few dozen keys: probing the LDS table costs more than resolving ids first (300 keys: 15 ms here,
+            // 6.6 ms as build pass + dense LDS group-by; crossover ~70 keys) -- the next executions of this plan go that way
+            static const int64_t ids_from = std::getenv("QE_IDS_FROM") ? std::atoll(std::getenv("QE_IDS_FROM")) : 64;
+            if (used > ids_from && ids_allowed && !plan.ids_overflow) plan.use_ids = true;
+            PoolScratch dense_scratch(ctx);   // (goes back to the pool before the table)
+            unsigned long long *d_dense = (unsigned long long *)dense_scratch.alloc((size_t)std::max<int64_t>(used, 1) * W * 8);
+            QE_HIP(hipMemsetAsync(ctx->d_ctrl, 0, 16, ctx->stream));
+            launch_ht_collect(ctx->stream, d_tab, C, W, d_dense, ctx->d_ctrl);
+            dense.resize((size_t)used * W);
+            if (used > 0) QE_HIP(hipMemcpyAsync(dense.data(), d_dense, dense.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+            QE_HIP(hipGetLastError());
+            QE_HIP(hipStreamSynchronize(ctx->stream));
+            m = used;
+            break;
+        }
+    }
+    return finish_hashed_groups(ctx, cg, dense.data(), m, agg_fns, nagg);
+}
+
+// HASH-PARTITIONED form of a hashed GROUP BY with many distinct keys (round 3): count -> scan -> scatter of
+// {header, aggregate inputs, key words} records by key HASH (the dense partitioned passes over a pseudo group id) -> ONE
+// workgroup per partition aggregates its records in an LDS hash table and appends the used entries to the result.  Every pass
+// streams; no gather, no global atomic per row.  nullptr: a partition held more distinct keys than its table has buckets (the
+// caller takes another path and remembers).
+// `skewed` (optional) is set, and nullptr returned before the scatter pass, when one partition holds several times its share of
+// the records (a key that owns a large part of the rows): ONE workgroup aggregates a partition, so that workgroup would run
+// alone for most of the pass -- the dense-id path slices its partitions and does not mind.
+qe_result *run_groupby_hp(qe_ctx *ctx, const qe_batch *batch, const std::shared_ptr<Plan> &plan, const int32_t *agg_fns, int32_t nagg,
+                          bool *skewed = nullptr) {
+    const CodegenOutput &cg = plan->cg;
+    const int64_t n = batch->nrows;
+    const int P = cg.nparts, HW = cg.hash_words;
+    const int waves = plan->geo.threads / 64;
+    const int64_t chunk_rows = plan->geo.chunk_rows() * waves;
+    const int64_t nchunks = (n + chunk_rows - 1) / chunk_rows;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nchunks, (int64_t)device_cus(ctx->device) * 8));
+    hipFunction_t f_count = nullptr, f_scatter = nullptr, f_agg = nullptr;
+    QE_HIP(hipModuleGetFunction(&f_count, plan->kernel.module, "qe_gb_count"));
+    QE_HIP(hipModuleGetFunction(&f_scatter, plan->kernel.module, "qe_gb_scatter"));
+    QE_HIP(hipModuleGetFunction(&f_agg, plan->kernel.module, "qe_gb_aggregate"));
+    PoolScratch temps(ctx);
+    auto talloc = [&](size_t bytes) { return temps.alloc(std::max<size_t>(bytes, 16)); };
+    uint32_t *d_counts = (uint32_t *)talloc((size_t)nchunks * P * 4);
+    unsigned long long *d_start = (unsigned long long *)talloc((size_t)(P + 1) * 8);
+    FusedParams p;
+    fill_inputs(p, batch, *plan);
+    p.nchunks = nchunks;
+    p.blk = (unsigned long long *)d_counts;
+    void *args[] = {&p};
+    if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    QE_HIP(hipModuleLaunchKernel(f_count, grid, 1, 1, plan->geo.threads, 1, 1, 0, ctx->stream, args, nullptr));
+    launch_gb_scan(ctx->stream, d_counts, nchunks, P, d_start);
+    std::vector<unsigned long long> start((size_t)P + 1, 0);
+    QE_HIP(hipMemcpyAsync(start.data(), d_start, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
+    QE_HIP(hipStreamSynchronize(ctx->stream));
+    unsigned long long m_records = 0;
+    for (int j = 0; j < P; j++) {
+        const unsigned long long cnt = start[j];
+        start[j] = m_records;
+        m_records += cnt;
+    }
+    start[P] = m_records;
+    if (m_records >= (1ull << 32)) return nullptr;   // record positions are 32-bit in the scatter pass
+    if (skewed) {
+        unsigned long long largest = 0;
+        for (int j = 0; j < P; j++) largest = std::max(largest, start[j + 1] - start[j]);
+        if (m_records > (1ull << 22) && largest > 3 * (m_records / (unsigned long long)P) + 65536) {
+            *skewed = true;
+            if (ctx->opts.profile) {   // (the bracket the caller reads must be closed)
+                QE_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+                QE_HIP(hipStreamSynchronize(ctx->stream));
+                collect_time(ctx);
+            }
+            return nullptr;
+        }
+    }
+    QE_HIP(hipMemcpyAsync(d_start, start.data(), (size_t)(P + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    // the groups' entries come back through pinned staging (64 MB for 1 M groups: 1.5 ms instead of ~15 ms into pageable memory)
+    unsigned long long *dense = nullptr;
+    struct PG { qe_ctx *c; unsigned long long **p; ~PG() { if (*p) c->pinned.release(*p); } } pg{ctx, &dense};
+    int64_t m = 0;
+    if (m_records > 0) {
+        p.l1 = d_start;
+        const int rec_words = 1 + cg.nvals;
+        static const bool dbg_times = std::getenv("QE_DEBUG_TIMES") != nullptr;
+        const auto t_alloc0 = std::chrono::steady_clock::now();
+        if (cg.hp_line_recs) p.desc = (unsigned long long *)talloc((size_t)(m_records / cg.hp_line_recs + 2) * 128);   // whole lines + the spare line
+        else p.desc = (unsigned long long *)talloc((size_t)(m_records + 16) * 8 * rec_words);
+        if (dbg_times)
+            std::fprintf(stderr, "run_groupby_hp: record array of %.2f GB from the pool in %.1f ms\n",
+                         (cg.hp_line_recs ? (double)(m_records / cg.hp_line_recs + 2) * 128 : (double)(m_records + 16) * 8 * rec_words) / 1e9,
+                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_alloc0).count());
+        const int sgrid = (int)std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)device_cus(ctx->device) * (plan->geo.threads >= 512 ? 1 : kScatterWgsPerCu)));
+        hipDeviceptr_t dbg = nullptr;
+        size_t dbg_bytes = 0;
+        if (debug_bit(ctx, kDbgScatterClocks)) {
+            QE_HIP(hipModuleGetGlobal(&dbg, &dbg_bytes, plan->kernel.module, "qe_dbg"));
+            QE_HIP(hipMemsetAsync(dbg, 0, dbg_bytes, ctx->stream));
+        }
+        QE_HIP(hipModuleLaunchKernel(f_scatter, sgrid, 1, 1, plan->geo.threads, 1, 1, 0, ctx->stream, args, nullptr));
+        if (dbg) {   // diagnostic build: shader clocks per phase, summed over the waves
+            unsigned long long h[8] = {};
+            QE_HIP(hipMemcpyAsync(h, dbg, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+            QE_HIP(hipStreamSynchronize(ctx->stream));
+            const double waves_total = (double)sgrid * waves;
+            std::fprintf(stderr, "qe_gb_scatter (hash-partitioned) phases, clocks per wave (grid %d x %d waves): issue loads %.0f | flush (stores) %.0f | "
+                         "LDS sort %.0f | wait loads + evaluate %.0f | chunk drain %.0f\n", sgrid, waves, h[0] / waves_total,
+                         h[1] / waves_total, h[2] / waves_total, h[3] / waves_total, h[4] / waves_total);
+        }
+        const int64_t cap = (int64_t)P * cg.part_groups;   // every bucket of every partition: cannot be exceeded
+        unsigned long long *d_out = (unsigned long long *)talloc((size_t)cap * HW * 8);
+        p.agg_partial = (double *)d_out;
+        p.capacity = cap;
+        p.ticket = ctx->d_ctrl;
+        p.error = ctx->d_ctrl + 1;
+        QE_HIP(hipMemsetAsync(ctx->d_ctrl, 0, 96, ctx->stream));
+        QE_HIP(hipModuleLaunchKernel(f_agg, P, 1, 1, 1024, 1, 1, 0, ctx->stream, args, nullptr));
+        if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        QE_HIP(hipMemcpyAsync(ctx->h_ctrl, ctx->d_ctrl, 16, hipMemcpyDeviceToHost, ctx->stream));
+        QE_HIP(hipStreamSynchronize(ctx->stream));
+        collect_time(ctx);
+        const unsigned int *hc = (const unsigned int *)ctx->h_ctrl;
+        if (hc[1] != 0) return nullptr;   // 6: some partition's table filled up
+        m = hc[0];
+        static const int64_t device_finish_from = std::getenv("QE_GROUPS_ON_DEVICE_FROM") ? std::atoll(std::getenv("QE_GROUPS_ON_DEVICE_FROM")) : 4096;
+        if (m >= (debug_bit(ctx, kDbgGroupsOnDevice) ? 1 : device_finish_from) && (int)cg.keys.size() <= 4 && nagg <= 8)
+            return finish_hashed_groups_on_device(ctx, cg, d_out, m, batch->nrows, agg_fns, nagg);
+        if (m > 0) {
+            dense = (unsigned long long *)ctx->pinned.alloc((size_t)m * HW * 8);
+            QE_HIP(hipMemcpyAsync(dense, d_out, (size_t)m * HW * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        QE_HIP(hipStreamSynchronize(ctx->stream));
+    } else {
+        if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        QE_HIP(hipStreamSynchronize(ctx->stream));
+        collect_time(ctx);
+    }
+    return finish_hashed_groups(ctx, cg, dense, m, agg_fns, nagg);
+}
+
+// GroupByAggregation over a dense group id (dictionary / boolean keys): LDS-privatised table, partitioned passes or global
+// atomics, the groups finished on the host in insertion order.
+qe_result *run_groupby_dense(qe_ctx *ctx, const qe_batch *batch, const std::shared_ptr<Plan> &plan, const int32_t *agg_fns, int32_t nagg) {
+    const CodegenOutput &cg = plan->cg;
+    const int64_t G = cg.ngroups;
+    const int W = cg.table_words;
+    // global accumulator table, initialised from the host (smallest row = ~0, MIN/MAX keys at their identity)
+    const int copies = cg.table_copies;
+    std::vector<unsigned long long> tab((size_t)G * W * copies);
+    for (int64_t g = 0; g < G * copies; g++) {
+        unsigned long long *e = &tab[(size_t)g * W];
+        e[0] = ~0ull;
+        for (int i = 0; i < nagg; i++) {
+            e[1 + 2 * i] = 0;
+            e[2 + 2 * i] = agg_fns[i] == QE_AGG_MIN ? 0x7fffffffffffffffull : agg_fns[i] == QE_AGG_MAX ? 0x8000000000000000ull : 0ull;
+        }
+    }
+    PoolScratch tab_scratch(ctx);
+    unsigned long long *d_tab = (unsigned long long *)tab_scratch.alloc(tab.size() * 8);
+    QE_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    const int64_t n = batch->nrows;
+    const bool no_partition = debug_bit(ctx, kDbgGroupByGlobalAtomics);   // keep the global-atomic path (A/B measurements, tests)
+    if (n > 0 && n < (1ll << 32) && cg.partitioned && !no_partition) {   // record positions are 32-bit in the scatter pass
+        // Domain too large for an LDS table: count -> scan -> scatter -> per-partition LDS aggregation
+        // (two streaming passes over the input and one over the records instead of one global atomic per value).
+        const int P = cg.nparts;
+        const int waves = plan->geo.threads / 64;
+        // a chunk = subs_per_chunk workgroup tiles (one sub-tile per wave each): the unit both passes hand to a workgroup
+        const int64_t chunk_rows = plan->geo.chunk_rows() * waves;
+        const int64_t nchunks = (n + chunk_rows - 1) / chunk_rows;
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nchunks, (int64_t)device_cus(ctx->device) * 8));
+        hipFunction_t f_count = nullptr, f_scatter = nullptr;
+        QE_HIP(hipModuleGetFunction(&f_count, plan->kernel.module, "qe_gb_count"));
+        QE_HIP(hipModuleGetFunction(&f_scatter, plan->kernel.module, "qe_gb_scatter"));
+        PoolScratch temps(ctx);
+        auto talloc = [&](size_t bytes) { return temps.alloc(std::max<size_t>(bytes, 16)); };
+        uint32_t *d_counts = (uint32_t *)talloc((size_t)nchunks * P * 4);
+        unsigned long long *d_start = (unsigned long long *)talloc((size_t)(P + 1) * 8);
+        FusedParams p;
+        fill_inputs(p, batch, *plan);
+        p.nchunks = nchunks;
+        p.blk = (unsigned long long *)d_counts;
+        void *args[] = {&p};
+        if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+        QE_HIP(hipModuleLaunchKernel(f_count, grid, 1, 1, plan->geo.threads, 1, 1, 0, ctx->stream, args, nullptr));
+        launch_gb_scan(ctx->stream, d_counts, nchunks, P, d_start);
+        std::vector<unsigned long long> start((size_t)P + 1, 0);
+        QE_HIP(hipMemcpyAsync(start.data(), d_start, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
+        QE_HIP(hipStreamSynchronize(ctx->stream));
+        unsigned long long m_records = 0;
+        for (int j = 0; j < P; j++) {
+            const unsigned long long cnt = start[j];
+            start[j] = m_records;
+            m_records += cnt;
+        }
+        start[P] = m_records;
+        QE_HIP(hipMemcpyAsync(d_start, start.data(), (size_t)(P + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (m_records > 0) {
+            p.l1 = d_start;
+            const int rec_words = 1 + cg.nvals;
+            if (m_records >= (1ull << 32)) fail(QE_ERR_UNSUPPORTED, "partitioned GROUP BY: more than 2^32 records");
+            p.desc = (unsigned long long *)talloc((size_t)(m_records + 16) * 8 * rec_words);   // + the spare line the scatter's idle threads write
+            // two workgroups per CU: the 64 KiB LDS stage of the tile sort lets two share a CU (one sorts and stores while the
+            // other waits for its loads)
+            static const int scatter_wgs = std::getenv("QE_GB_SCATTER_WGS_PER_CU") ? std::atoi(std::getenv("QE_GB_SCATTER_WGS_PER_CU")) : kScatterWgsPerCu;
+            const int sgrid = (int)std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)device_cus(ctx->device) * (plan->geo.threads >= 512 ? 1 : std::max(1, scatter_wgs))));
+            hipDeviceptr_t dbg = nullptr;
+            size_t dbg_bytes = 0;
+            if (debug_bit(ctx, kDbgScatterClocks)) {
+                QE_HIP(hipModuleGetGlobal(&dbg, &dbg_bytes, plan->kernel.module, "qe_dbg"));
+                QE_HIP(hipMemsetAsync(dbg, 0, dbg_bytes, ctx->stream));
+            }
+            QE_HIP(hipModuleLaunchKernel(f_scatter, sgrid, 1, 1, plan->geo.threads, 1, 1, 0, ctx->stream, args, nullptr));
+            if (dbg) {   // diagnostic build: shader clocks per phase, summed over the waves
+                unsigned long long h[8] = {};
+                QE_HIP(hipMemcpyAsync(h, dbg, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+                QE_HIP(hipStreamSynchronize(ctx->stream));
+                const double waves_total = (double)sgrid * waves;
+                std::fprintf(stderr, "qe_gb_scatter phases, clocks per wave (grid %d x %d waves): issue loads %.0f | flush (stores) %.0f | "
+                             "LDS sort %.0f | wait loads + evaluate %.0f | chunk drain %.0f\n", sgrid, waves, h[0] / waves_total,
+                             h[1] / waves_total, h[2] / waves_total, h[3] / waves_total, h[4] / waves_total);
+            }
+            // pass 3 (generated per plan): ~512 workgroups, one LDS table each, merged into the global table
+            static const int agg_wgs = std::getenv("QE_GB_AGG_WGS") ? std::atoi(std::getenv("QE_GB_AGG_WGS")) : 512;
+            const int slices = std::max(1, std::min(64, agg_wgs / P));
+            const size_t lds = (size_t)cg.part_groups * W * 8;
+            const int agg_threads = lds > 48 * 1024 ? 1024 : 256;   // a table that leaves room for one workgroup per CU: make it a big one
+            hipFunction_t f_agg = nullptr;
+            QE_HIP(hipModuleGetFunction(&f_agg, plan->kernel.module, "qe_gb_aggregate"));
+            p.agg_partial = (double *)d_tab;
+            QE_HIP(hipModuleLaunchKernel(f_agg, slices, P, 1, agg_threads, 1, 1, 0, ctx->stream, args, nullptr));
+        }
+        if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        QE_HIP(hipStreamSynchronize(ctx->stream));   // the temporaries go back to the pool when this scope ends
+    } else if (n > 0) {
+        const int64_t sub_rows = plan->geo.sub_rows();
+        const int64_t ntiles = (n + sub_rows - 1) / sub_rows;
+        const int waves = plan->geo.threads / 64;
+        const int wgs_per_cu = plan->geo.threads >= 1024 ? 1 : 4;   // a 1024-thread workgroup owns its CU (and merges its table once)
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + waves - 1) / waves, (int64_t)device_cus(ctx->device) * wgs_per_cu));
+        FusedParams p;
+        fill_inputs(p, batch, *plan);
+        p.agg_partial = (double *)d_tab;
+        launch_fused(ctx, *plan, p, grid);
+    }
+    QE_HIP(hipMemcpyAsync(tab.data(), d_tab, tab.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    QE_HIP(hipStreamSynchronize(ctx->stream));
+    if (n > 0) collect_time(ctx);
+    // fold the per-XCD copies into copy 0, in XCD order
+    for (int c = 1; c < copies; c++) {
+        for (int64_t g = 0; g < G; g++) {
+            unsigned long long *d = &tab[(size_t)g * W];
+            const unsigned long long *e = &tab[((size_t)c * G + g) * W];
+            if (e[0] == ~0ull) continue;
+            d[0] = std::min(d[0], e[0]);
+            for (int i = 0; i < nagg; i++) {
+                if (e[1 + 2 * cg.cnt_src[i]] == 0) continue;
+                if (cg.cnt_src[i] == i) d[1 + 2 * i] += e[1 + 2 * i];
+                if (agg_fns[i] == QE_AGG_SUM || agg_fns[i] == QE_AGG_AVG) {
+                    double a, b;
+                    std::memcpy(&a, &d[2 + 2 * i], 8);
+                    std::memcpy(&b, &e[2 + 2 * i], 8);
+                    a += b;
+                    std::memcpy(&d[2 + 2 * i], &a, 8);
+                } else if (agg_fns[i] == QE_AGG_MIN) {
+                    d[2 + 2 * i] = (unsigned long long)std::min((long long)d[2 + 2 * i], (long long)e[2 + 2 * i]);
+                } else if (agg_fns[i] == QE_AGG_MAX) {
+                    d[2 + 2 * i] = (unsigned long long)std::max((long long)d[2 + 2 * i], (long long)e[2 + 2 * i]);
+                }
+            }
+        }
+    }
+    // groups in insertion order = ascending first row (LinkedHashMap order, GroupByAggregationOperator.kt:22)
+    std::vector<std::pair<unsigned long long, int64_t>> order;
+    for (int64_t g = 0; g < G; g++)
+        if (tab[(size_t)g * W] != ~0ull) order.emplace_back(tab[(size_t)g * W], g);
+    std::sort(order.begin(), order.end());
+    const int64_t m = (int64_t)order.size();
+    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [ctx](qe_result *r) { free_result(ctx, r); });
+    res->count = m;
+    res->capacity = m;
+    const size_t words = (size_t)std::max<int64_t>(1, (m + 63) / 64);
+    auto upload = [&](const void *src, size_t bytes) -> void * {
+        void *d = ctx->pool.alloc(std::max<size_t>(bytes, 16));
+        if (bytes) QE_HIP(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return d;
+    };
+    std::vector<std::vector<unsigned long long>> keep_words;   // host staging must outlive the async copies
+    std::vector<std::vector<int32_t>> keep_codes;
+    std::vector<std::vector<double>> keep_vals;
+    int64_t stride = 1;
+    for (size_t k = 0; k < cg.keys.size(); k++) {
+        const int domain = cg.key_domain[k];
+        OutColumn oc;
+        oc.type = cg.keys[k].type;
+        oc.dict = cg.keys[k].dict;
+        oc.dict_handle.d = oc.dict;
+        std::vector<unsigned long long> valid(words, 0), bits(words, 0);
+        std::vector<int32_t> codes((size_t)std::max<int64_t>(m, 1), 0);
+        bool any_null = false;
+        for (int64_t j = 0; j < m; j++) {
+            const int code = (int)((order[j].second / stride) % (domain + 1));
+            if (code == domain) { any_null = true; continue; }
+            valid[j >> 6] |= 1ull << (j & 63);
+            codes[j] = code;
+            if (code) bits[j >> 6] |= 1ull << (j & 63);
+        }
+        oc.nullable = any_null;
+        if (oc.type == QE_BOOLEAN) {
+            keep_words.push_back(bits);
+            oc.data = upload(keep_words.back().data(), words * 8);
+        } else {
+            keep_codes.push_back(codes);
+            oc.data = upload(keep_codes.back().data(), (size_t)m * 4);
+        }
+        if (any_null) {
+            keep_words.push_back(valid);
+            oc.validity = (uint64_t *)upload(keep_words.back().data(), words * 8);
+        }
+        res->cols.push_back(oc);
+        stride *= (domain + 1);
+    }
+    for (int i = 0; i < nagg; i++) {
+        OutColumn oc;
+        oc.type = QE_DOUBLE;
+        std::vector<double> vals((size_t)std::max<int64_t>(m, 1), 0.0);
+        std::vector<unsigned long long> valid(words, 0);
+        bool any_null = false;
+        for (int64_t j = 0; j < m; j++) {
+            const unsigned long long *e = &tab[(size_t)order[j].second * W];
+            const unsigned long long cnt = e[1 + 2 * cg.cnt_src[i]];
+            const unsigned long long raw = e[2 + 2 * i];
+            double v = 0.0;
+            bool ok = true;
+            switch (agg_fns[i]) {
+            case QE_AGG_COUNT: v = (double)cnt; break;                       // Accumulators.kt:26-36
+            case QE_AGG_SUM: std::memcpy(&v, &raw, 8); ok = cnt != 0; break;  // :47-53 empty => null
+            case QE_AGG_AVG: std::memcpy(&v, &raw, 8); ok = cnt != 0; if (ok) v /= (double)cnt; break;
+            default: {                                                        // MIN / MAX: undo the ordered key
+                long long key = (long long)raw;
+                long long b = key ^ ((key >> 63) & 0x7fffffffffffffffll);
+                std::memcpy(&v, &b, 8);
+                ok = cnt != 0;
+            }
+            }
+            if (ok) valid[j >> 6] |= 1ull << (j & 63);
+            else { any_null = true; v = 0.0; }
+            vals[j] = v;
+        }
+        oc.nullable = any_null;
+        keep_vals.push_back(vals);
+        oc.data = upload(keep_vals.back().data(), (size_t)m * 8);
+        if (any_null) {
+            keep_words.push_back(valid);
+            oc.validity = (uint64_t *)upload(keep_words.back().data(), words * 8);
+        }
+        res->cols.push_back(oc);
+    }
+    QE_HIP(hipStreamSynchronize(ctx->stream));
+    return res.release();
+}
+
+// ---- hashed GROUP BY: the choice of the route -----------------------------------------------------------------
+
+// the widest table a partition of the hash-partitioned form may have, as log2 of its buckets: entry = {first row, key words..,
+// the counters and accumulators the plan needs}: {first row, key, MIN, MAX} and {first row, key, count, SUM} are 32 bytes:
+// 4096 buckets in 128 KiB
+int hp_max_shift(const AggregateCall &q, const CodegenOutput &cg) {
+    int max_shift = 12;
+    bool keys_nullable = false;
+    std::vector<char> agg_nullable;
+    for (int i = 0; i < q.nagg; i++) agg_nullable.push_back(cg.outs[(size_t)i].nullable ? 1 : 0);
+    for (const OutSpec &ks : cg.keys) keys_nullable = keys_nullable || ks.nullable;
+    const int64_t entry_bytes = 8 * (1 + q.nkeys + (keys_nullable ? 1 : 0) + hp_entry_layout(agg_nullable, q.agg_fns, q.nagg).words);
+    while (max_shift > 8 && (entry_bytes << max_shift) > 144 * 1024) max_shift--;
+    return max_shift;
+}
+
+// one attempt at the hash-partitioned form with P partitions of 2^shift buckets: the result, or nullptr when some partition's
+// table filled up (or the form is not to be had: plan->hp_failed)
+qe_result *try_hp(const AggregateCall &q, const std::shared_ptr<Plan> &plan, int P, int shift) {
+    std::shared_ptr<Plan> hplan;
+    try {
+        PlanRequest rq = q.request();
+        rq.hp_parts = P;
+        rq.hp_shift = shift;
+        hplan = get_plan(q.ctx, q.batch, rq);
+    } catch (const Error &) {   // e.g. an entry too wide for the LDS table: the other forms stay
+        plan->hp_failed = true;
+        return nullptr;
+    }
+    if (!hplan || !hplan->cg.hp) return nullptr;
+    qe_result *r = nullptr;
+    bool skewed = false;
+    try {
+        r = run_groupby_hp(q.ctx, q.batch, hplan, q.agg_fns, q.nagg, &skewed);
+    } catch (const Error &e) {
+        // its record array (21 - 64 bytes per kept row) did not fit beside the batch: the dense-id path needs 4 + 16
+        // bytes per row -- this plan stays with that one (run_groupby_hp releases what it had allocated)
+        if (e.code != QE_ERR_OOM) throw;
+        plan->hp_failed = true;
+    }
+    if (skewed) plan->hp_failed = true;   // a property of the data: this plan stays with the forms that slice their work
+    if (r) {
+        plan->known_keys = r->count;
+        q.ctx->last_form = QE_FORM_GROUPBY_HASH_PARTITIONED;
+    }
+    return r;
+}
+
+qe_result *run_groupby_hashed_route(const AggregateCall &q, const std::shared_ptr<Plan> &plan) {
+    qe_ctx *ctx = q.ctx;
+    const qe_batch *batch = q.batch;
+    // many distinct keys (known from an earlier execution of this plan): the hash-partitioned form -- every pass
+    // streams -- instead of the id build + dense passes (100 000 DOUBLE keys, 1 B rows: 24 ms that way)
+    // measured, SELECT k, MIN(v), MAX(v) over 1 B rows, id build + dense passes against this form: 30 000 keys 21 / 14.7 ms,
+    // 100 000 keys 24.0 / 15.3, 300 000 keys 32.1 / 17.8, 1 000 000 keys 57 / 24.4 ; below 25 000 keys, this form / ids:
+    // 20 000 keys 14.9 / 20.2, 10 000 keys 15.9 / 16.9, 5000 keys 16.3 / 16.8, 3000 keys 17.2 / 18.3 (fewer fit the LDS-privatised table)
+    static const int64_t hp_from = std::getenv("QE_HP_FROM") ? std::atoll(std::getenv("QE_HP_FROM")) : 4000;
+    const bool hp_forced = debug_bit(ctx, kDbgForceHashPartitioned), hp_never = debug_bit(ctx, kDbgNeverHashPartitioned);
+    const int64_t n = batch->nrows;
+    const bool hp_possible = !hp_never && !plan->hp_failed && n > 0 && n < (1ll << 32) && q.nkeys <= 4 && q.nagg <= 8;
+    static const int env_parts = std::getenv("QE_HP_PARTS") ? std::atoi(std::getenv("QE_HP_PARTS")) : 0;
+    static const int env_shift = std::getenv("QE_HP_SHIFT") ? std::atoi(std::getenv("QE_HP_SHIFT")) : 0;
+    static const int env_fill = std::getenv("QE_HP_FILL") ? std::atoi(std::getenv("QE_HP_FILL")) : 16;
+    const int max_shift = hp_max_shift(q, plan->cg);
+    if (hp_possible && (hp_forced || (plan->known_keys >= hp_from && n >= (4ll << 20)))) {
+        // ONE workgroup aggregates a partition (128 partitions left half the chip idle: 21.8 ms for the aggregation of 1 B
+        // records).  Fewer partitions make longer runs per scatter tile -- less padding to whole lines --, more partitions keep
+        // the tables sparse.  Buckets for ~16x the keys seen, 256 .. 4096 per partition: a wave leaves the probe loop after its LONGEST
+        // probe sequence, so the tables are as sparse as the LDS allows (100 000 keys, 256 partitions x 1024 / 2048 / 4096 buckets:
+        // 23.4 / 17 / 15.5 ms)
+        const int64_t keys_seen = std::max<int64_t>(plan->known_keys, 1);
+        // few partitions = long runs per scatter tile = little padding, and the probe loop tolerates full tables better than the
+        // scatter tolerates short runs (1 M keys, 1 B rows: 512 partitions half full 24.6 ms, 1024 partitions a quarter full
+        // 37.1 ms; 500 000 keys: 256 partitions half full 22.6 ms, 512 a quarter full 18.3 ms): 256 partitions up to 30 %, 512
+        // up to 50 %, 1024 beyond
+        int P = keys_seen * 10 <= ((int64_t)256 << max_shift) * 3 ? 256 : keys_seen * 2 <= ((int64_t)512 << max_shift) ? 512 : 1024;
+        if (hp_forced && plan->known_keys <= 0) P = 64;
+        if (env_parts >= 2) P = env_parts;
+        int shift = 8;
+        while (shift < max_shift && ((int64_t)P << shift) < keys_seen * env_fill) shift++;
+        if (env_shift >= 6) shift = env_shift;
+        if (qe_result *r = try_hp(q, plan, P, shift)) return r;
+        // some partition's table filled up: with 1024 partitions there is nothing larger to try; otherwise the run below
+        // reports how many keys there are and the next execution sizes its partitions from that
+        if (P >= 1024) plan->hp_failed = true;
+    }
+    // The FIRST execution of a plan does not know its keys.  The LDS tables and the id build find out cheaply that there are
+    // many (their launches stop at once when a table fills up: more than 32 768 keys fill the id build's first table); from
+    // there the hash-partitioned form takes over with the widest tables -- 256, then 512, then 1024 partitions when a table
+    // overflows -- instead of growing the id table (100 000 keys, 1 B rows: a first execution of 48 ms that way).
+    bool many_keys = false;
+    const bool first_hp = hp_possible && !hp_forced && plan->known_keys < 0 && plan->id_capacity <= 0 && n >= (4ll << 20);
+    qe_result *out = run_groupby_hashed(ctx, batch, *plan, q.filter, q.exprs, q.agg_fns, q.nagg, first_hp ? &many_keys : nullptr);
+    if (!out && many_keys) {
+        for (int P = 256; P <= 1024 && !out && !plan->hp_failed; P *= 2) out = try_hp(q, plan, P, max_shift);
+        if (out) return out;
+        out = run_groupby_hashed(ctx, batch, *plan, q.filter, q.exprs, q.agg_fns, q.nagg, nullptr);   // more keys than 1024 tables hold
+    }
+    if (out) plan->known_keys = out->count;
+    ctx->last_form = QE_FORM_GROUPBY_HASHED;
+    return out;
+}
+
+}  // namespace
+
+namespace qe {
+
+qe_result *run_groupby(const AggregateCall &q) {
+    auto plan = get_plan(q.ctx, q.batch, q.request());
+    if (plan->cg.hashed) return run_groupby_hashed_route(q, plan);
+    qe_result *out = run_groupby_dense(q.ctx, q.batch, plan, q.agg_fns, q.nagg);
+    q.ctx->last_form = QE_FORM_GROUPBY_DENSE;
+    return out;
+}
+
+// The global aggregate: every workgroup leaves {(acc, count) per aggregate, selected rows}, folded on the host.
+void run_global_aggregate(const AggregateCall &q, double *out_values, uint8_t *out_valid, int64_t *out_selected_rows) {
+    qe_ctx *ctx = q.ctx;
+    const qe_batch *batch = q.batch;
+    const int32_t *agg_fns = q.agg_fns;
+    const int32_t nagg = q.nagg;
+    auto plan = get_plan(ctx, batch, q.request());
+    const int64_t n = batch->nrows;
+    const int64_t sub_rows = plan->geo.sub_rows();
+    const int64_t ntiles = (n + sub_rows - 1) / sub_rows;
+    // fixed grid => fixed reduction tree => bitwise reproducible sums on a given device
+    const int waves = plan->geo.threads / 64;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + waves - 1) / waves,
+                                                                  (int64_t)device_cus(ctx->device) * 8));
+    const int stride = 2 * nagg + 1;
+    std::vector<double> partial((size_t)grid * stride, 0.0);
+    if (ntiles > 0) {
+        FusedParams p;
+        fill_inputs(p, batch, *plan);
+        PoolScratch scratch(ctx);
+        double *d_partial = (double *)scratch.alloc(partial.size() * 8);
+        p.agg_partial = d_partial;
+        p.nchunks = ntiles;
+        launch_fused(ctx, *plan, p, grid);
+        QE_HIP(hipMemcpyAsync(partial.data(), d_partial, partial.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        QE_HIP(hipStreamSynchronize(ctx->stream));
+        collect_time(ctx);
+    }
+    int64_t nsel = 0;
+    for (int i = 0; i < nagg; i++) {
+        const int fn = agg_fns[i];
+        double acc = fn == QE_AGG_MIN ? INFINITY : fn == QE_AGG_MAX ? -INFINITY : 0.0;
+        double cnt = 0;
+        if (ntiles > 0)
+            for (int b = 0; b < grid; b++) {
+                const double a = partial[(size_t)b * stride + 2 * i], c = partial[(size_t)b * stride + 2 * i + 1];
+                cnt += c;
+                if (fn == QE_AGG_MIN) acc = (a != a || acc != acc) ? (acc != acc ? acc : a)
+                                          : (a == 0.0 && acc == 0.0 ? (std::signbit(acc) ? acc : a) : std::min(acc, a));
+                else if (fn == QE_AGG_MAX) acc = (a != a || acc != acc) ? (acc != acc ? acc : a)
+                                               : (a == 0.0 && acc == 0.0 ? (std::signbit(acc) ? a : acc) : std::max(acc, a));
+                else acc += a;
+            }
+        if (fn == QE_AGG_COUNT) {           // Accumulators.kt:26-36
+            out_values[i] = cnt;
+            out_valid[i] = 1;
+        } else if (cnt == 0) {              // :47-53 empty => null
+            out_values[i] = 0.0;
+            out_valid[i] = 0;
+        } else {
+            out_values[i] = fn == QE_AGG_AVG ? acc / cnt : acc;   // :101-107
+            out_valid[i] = 1;
+        }
+    }
+    if (ntiles > 0)
+        for (int b = 0; b < grid; b++) nsel += (int64_t)partial[(size_t)b * stride + 2 * nagg];
+    if (out_selected_rows) *out_selected_rows = nsel;
+}
+
+}  // namespace qe
+
+extern "C" {
+
+int32_t qe_filter_aggregate_prepare(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filter,
+                                    const qe_expr *const *exprs, const int32_t *agg_fns, int32_t nagg) {
+    if (!ctx || !batch || nagg <= 0 || !exprs || !agg_fns) return QE_ERR_INVALID_ARG;
+    return guarded(ctx, [&] {
+        if (ctx->device >= 0) need_device(ctx);
+        const AggregateCall q{ctx, batch, filter, nullptr, 0, exprs, agg_fns, nagg};
+        (void)get_plan(ctx, batch, q.request(ctx->device >= 0));
+    });
+}
+
+int32_t qe_filter_aggregate(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filter, const qe_expr *const *exprs,
+                            const int32_t *agg_fns, int32_t nagg, double *out_values, uint8_t *out_valid,
+                            int64_t *out_selected_rows) {
+    if (!ctx || !batch || nagg <= 0 || !exprs || !agg_fns || !out_values || !out_valid) return QE_ERR_INVALID_ARG;
+    return guarded(ctx, [&] {
+        need_device(ctx);
+        if (batch->schema_only) fail(QE_ERR_INVALID_ARG, "schema-only batch (qe_batch_describe) cannot be executed");
+        run_global_aggregate({ctx, batch, filter, nullptr, 0, exprs, agg_fns, nagg}, out_values, out_valid, out_selected_rows);
+    });
+}
+
+int32_t qe_filter_groupby_prepare(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filter, const qe_expr *const *keys,
+                                  int32_t nkeys, const qe_expr *const *exprs, const int32_t *agg_fns, int32_t nagg) {
+    if (!ctx || !batch || nkeys <= 0 || !keys || nagg <= 0 || !exprs || !agg_fns) return QE_ERR_INVALID_ARG;
+    return guarded(ctx, [&] {
+        if (ctx->device >= 0) need_device(ctx);
+        const AggregateCall q{ctx, batch, filter, keys, nkeys, exprs, agg_fns, nagg};
+        PlanRequest rq = q.request(ctx->device >= 0);
+        auto plan = get_plan(ctx, batch, rq);
+        if (plan->cg.hashed && debug_bit(ctx, kDbgForceHashPartitioned) && nkeys <= 4 && nagg <= 8) {   // forced hash-partitioned form: its plan too
+            rq.hp_parts = 64;
+            rq.hp_shift = 8;
+            (void)get_plan(ctx, batch, rq);
+        }
+    });
+}
+
+int32_t qe_filter_groupby(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filter, const qe_expr *const *keys, int32_t nkeys,
+                          const qe_expr *const *exprs, const int32_t *agg_fns, int32_t nagg, qe_result **out) {
+    if (!ctx || !batch || !out || nkeys <= 0 || !keys || nagg <= 0 || !exprs || !agg_fns) return QE_ERR_INVALID_ARG;
+    *out = nullptr;
+    return guarded(ctx, [&] {
+        need_device(ctx);
+        if (batch->schema_only) fail(QE_ERR_INVALID_ARG, "schema-only batch (qe_batch_describe) cannot be executed");
+        *out = run_groupby({ctx, batch, filter, keys, nkeys, exprs, agg_fns, nagg});
+    });
+}
+
+}  // extern "C"

@@ -444,7 +444,58 @@ struct qe_host_result {
     bool waited = false;
 };
 
-// internals shared by qe_api.cpp and qe_comm.cpp (the overlapped scan + exchange)
+namespace qe {
+
+// Scratch buffers of one call from the context's device pool: alloc() hands them out, the destructor gives every one of them
+// back, in the order they were handed out (the order decides which of two equally sized buffers the pool reuses first).
+class __attribute__((visibility("hidden"))) PoolScratch {
+public:
+    explicit PoolScratch(qe_ctx *ctx) : ctx_(ctx) {}
+    PoolScratch(const PoolScratch &) = delete;
+    PoolScratch &operator=(const PoolScratch &) = delete;
+    ~PoolScratch() { for (void *p : bufs_) ctx_->pool.release(p); }
+    void *alloc(size_t bytes) {
+        bufs_.push_back(nullptr);   // (the slot first: a buffer the pool has handed out is never lost)
+        return bufs_.back() = ctx_->pool.alloc(bytes);
+    }
+
+private:
+    qe_ctx *ctx_;
+    std::vector<void *> bufs_;
+};
+
+// The bits of qe_options.tuning[5]: measurement and test switches, not API.
+enum DebugBit : int {
+    kDbgAblationMask = 255,            // bits 1 .. 128 reach the generator (CodegenInput::debug_mask): ablation and diagnostic BUILDS
+    kDbgWaitStats = 16,                // ring kernel: wait statistics to stderr
+    kDbgTrace = 32,                    // ring / dense kernel: per-chunk trace (to $QE_TRACE_FILE)
+    kDbgScatterClocks = 64,            // partitioned group-by: shader clocks per phase of the scatter pass to stderr
+    kDbgGroupByGlobalAtomics = 256,    // dense group-by through global atomics instead of partitions
+    kDbgForceTwoPass = 512,
+    kDbgNeverTwoPass = 1024,
+    kDbgNoLateMaterialisation = 2048,  // load every column for every row
+    kDbgOneFilterLoadStage = 4096,     // every filter column in the first load stage
+    kDbgNoGeometryChoice = 8192,       // default geometry only
+    kDbgForceDense = 16384,
+    kDbgNeverDense = 32768,
+    kDbgNoSelectivitySample = 65536,   // no sample before a plan's first execution
+    kDbgHashedGlobalAtomics = 131072,  // hashed group-by keeps the global-atomic form instead of dense ids
+    kDbgForceLocal = 262144,
+    kDbgNeverLocal = 524288,
+    kDbgWrittenConjunctOrder = 1048576,
+    kDbgNoPrefetch = 2097152,          // no stage-0 prefetch
+    kDbgAlwaysPrefetch = 4194304,      // .. for every staged plan
+    kDbgForceHashPartitioned = 8388608,
+    kDbgNeverHashPartitioned = 16777216,
+    kDbgHpRecords = 33554432,          // hash-partitioned group-by: {header, words} records instead of lines of records
+    kDbgGroupsOnDevice = 67108864,     // .. its groups are finished on the device whatever their number
+};
+inline bool debug_bit(const qe_ctx *ctx, DebugBit b) { return (ctx->opts.tuning[5] & b) != 0; }
+
+}  // namespace qe
+
+// internals of qe_api.cpp that qe_comm.cpp calls (the overlapped scan + exchange); qe_exec.h has what the files behind the
+// C ABI share among themselves
 std::vector<int64_t> qe_int_count_slices(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filter, const qe_expr *const *projs, int32_t nproj,
                                          int64_t *slice_rows_io, int32_t nslices);
 qe_result *qe_int_run_fused_slice(qe_ctx *ctx, const qe_batch *batch, int64_t row_begin, int64_t nrows, const qe_expr *filter,
