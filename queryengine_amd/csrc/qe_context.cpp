@@ -309,10 +309,13 @@ int32_t qe_batch_create(qe_ctx *ctx, int64_t nrows, int32_t ncols, const qe_col_
             c.data = ctx->pool.alloc(std::max<size_t>(nb, 16));
             b->cols.push_back(c);
             if (nb) QE_HIP(hipMemcpyAsync(c.data, cols[j].data, nb, hipMemcpyHostToDevice, ctx->stream));
-            if (cols[j].validity && nrows > 0) {
-                b->cols.back().validity = (uint64_t *)ctx->pool.alloc(bitmap_bytes(nrows));
-                QE_HIP(hipMemcpyAsync(b->cols.back().validity, cols[j].validity, bitmap_bytes(nrows),
-                                      hipMemcpyHostToDevice, ctx->stream));
+            if (cols[j].validity) {
+                // also for an empty batch: nullability is part of the plan key, and the empty batch of a stream must find the
+                // plan of its schema, not compile one for a schema without nulls
+                b->cols.back().validity = (uint64_t *)ctx->pool.alloc(std::max<size_t>(bitmap_bytes(nrows), 16));
+                if (nrows > 0)
+                    QE_HIP(hipMemcpyAsync(b->cols.back().validity, cols[j].validity, bitmap_bytes(nrows),
+                                          hipMemcpyHostToDevice, ctx->stream));
             }
         }
         QE_HIP(hipStreamSynchronize(ctx->stream));   // host buffers may be reused by the caller

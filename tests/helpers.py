@@ -65,6 +65,66 @@ def assert_columns_equal(got: Column, want: Column, what: str = "") -> None:
     assert bad.size == 0, f"{what}: values differ at valid-row ordinals {bad[:8]}: got {g[bad[:8]]!r} want {w[bad[:8]]!r}"
 
 
+def _rows_equal(got, want, nkeys, aggs, oracle):
+    """Group-by rows [key values.., aggregate values..] against the oracle's, value by value: same groups in the same (insertion)
+    order, keys by Double.equals, COUNT / MIN / MAX / SUM exact (the tests feed integer-valued doubles), AVG within 1e-12."""
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        for a, b in zip(g[:nkeys], w[:nkeys]):                 # same groups, same (insertion) order; Double.equals on keys
+            if isinstance(b, float):
+                assert a is not None and (a == b and np.signbit(a) == np.signbit(b) or (a != a and b != b)), (g, w)
+            else:
+                assert a == b, (g, w)
+        for a, b, fn in zip(g[nkeys:], w[nkeys:], aggs):
+            if b is None or fn != oracle.AVG:
+                assert a == b or (a != a and b != b), (g, w)
+            else:
+                assert abs(a - b) <= 1e-12 * max(1.0, abs(b))
+
+
+def group_rows_to_columns(rows, key_types: Sequence[DataType], nagg: int) -> List[Column]:
+    """The oracle's group-by rows (numeric keys only) as columns: one per key in its type, one DOUBLE column per aggregate,
+    None => not valid.  Made once per batch, so that every later comparison is a handful of array operations."""
+    m = len(rows)
+    out = []
+    for j in range(len(key_types) + nagg):
+        t = key_types[j] if j < len(key_types) else D
+        assert t in (D, I64, I32), t
+        valid = np.fromiter((r[j] is not None for r in rows), dtype=bool, count=m)
+        dt = {D: np.float64, I64: np.int64, I32: np.int32}[t]
+        data = np.fromiter((r[j] if r[j] is not None else 0 for r in rows), dtype=dt, count=m)
+        out.append(Column(t, data, valid))
+    return out
+
+
+def assert_group_columns_equal(got: Sequence[Column], want: Sequence[Column], nkeys: int, aggs, avg_fn, what: str = "") -> None:
+    """_rows_equal on whole columns, the same rules: the same number of groups; per column the same null positions; keys where
+    valid by Double.equals (bit for bit, every NaN the same key) or integer equality; aggregates where valid `==` or both NaN,
+    AVG within 1e-12 * max(1, |want|).  Row g of `got` is compared with row g of `want`: the order of the groups counts."""
+    assert len(got) == len(want) == nkeys + len(aggs), f"{what}: {len(got)} columns, want {len(want)}"
+    for j, (g, w) in enumerate(zip(got, want)):
+        name = f"{what}: column {j}"
+        assert len(g) == len(w), f"{name}: {len(g)} groups, want {len(w)}"
+        m = len(w)
+        gv = g.valid if g.valid is not None else np.ones(m, dtype=bool)
+        wv = w.valid if w.valid is not None else np.ones(m, dtype=bool)
+        bad = np.nonzero(gv != wv)[0]
+        assert bad.size == 0, f"{name}: null positions differ at groups {bad[:8]} (got valid = {gv[bad[:8]]})"
+        a, b = g.data[wv], w.data[wv]
+        if j < nkeys:
+            assert g.type == w.type, f"{name}: type {g.type} != {w.type}"
+            if w.type == D:
+                same = (a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))
+            else:
+                same = a == b
+        elif aggs[j - nkeys] == avg_fn:
+            same = np.abs(a - b) <= 1e-12 * np.maximum(1.0, np.abs(b))
+        else:
+            same = (a == b) | (np.isnan(a) & np.isnan(b))
+        bad = np.nonzero(~same)[0]
+        assert bad.size == 0, f"{name}: differs at valid-group ordinals {bad[:8]}: got {a[bad[:8]]!r} want {b[bad[:8]]!r}"
+
+
 SPECIAL_F64 = [0.0, -0.0, 1.0, -1.0, 0.5, 2.5, 100.0, -7.5, 7.5, float("inf"), float("-inf"), float("nan"),
                5e-324, -5e-324, 1.7976931348623157e308, 2.0 ** 53, -(2.0 ** 53), 1e-300, 3.0, 99.99999999999999]
 SPECIAL_I64 = [0, 1, -1, 2, -2, 100, 99, 101, 2 ** 31, -(2 ** 31), 2 ** 53, -(2 ** 53), 2 ** 63 - 1, -(2 ** 63), 7, -7,

@@ -12,6 +12,8 @@ from queryengine_amd.operators import GpuFilterProjectOperator, GpuGlobalAggrega
 from queryengine_amd.planner import Mode, buildLogicalPlan, buildPhysicalPlan, query
 from queryengine_amd.sql import parseQuery
 
+from helpers import _rows_equal
+
 pytestmark = pytest.mark.gpu
 D, I64, I32, B, S = DataType.DOUBLE, DataType.INT64, DataType.INT32, DataType.BOOLEAN, DataType.STRING
 GOLDEN = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_vectors.json")))
@@ -372,21 +374,6 @@ def test_group_by_counter_sharing_with_mixed_nullability(path, oracle):
                     assert abs(a - b) <= 1e-12 * max(1.0, abs(b))
     batch.free()
     ctx.close()
-
-
-def _rows_equal(got, want, nkeys, aggs, oracle):
-    assert len(got) == len(want)
-    for g, w in zip(got, want):
-        for a, b in zip(g[:nkeys], w[:nkeys]):                 # same groups, same (insertion) order; Double.equals on keys
-            if isinstance(b, float):
-                assert a is not None and (a == b and np.signbit(a) == np.signbit(b) or (a != a and b != b)), (g, w)
-            else:
-                assert a == b, (g, w)
-        for a, b, fn in zip(g[nkeys:], w[nkeys:], aggs):
-            if b is None or fn != oracle.AVG:
-                assert a == b or (a != a and b != b), (g, w)
-            else:
-                assert abs(a - b) <= 1e-12 * max(1.0, abs(b))
 
 
 @pytest.mark.parametrize("case", ["double_specials", "double_specials_many", "int64_many", "int64_many_global_atomics", "mixed_keys", "grows",
