@@ -349,6 +349,65 @@ int32_t qe_result_order_by_keys(qe_ctx *ctx, const qe_result *result, const qe_s
  * out[3] selection passes run */
 int32_t qe_ctx_last_sort_stats(const qe_ctx *ctx, int64_t out[4]);
 
+/* ---- hash equi-join of two device-resident sides ---------------------------------------------------------
+ * The reference has no join (Query.g4 reads one table); this is the fact-to-dimension step that follows its operators.
+ * A side is a result or a batch.  qe_join_build reads the build side's key columns once and keeps a table: the rows
+ * whose key holds no NULL, sorted stably by the top bits of a 64-bit hash of the key, and a directory over those bits.
+ * qe_join_probe joins a probe side against it and returns an ordinary result.
+ *
+ * Keys: 1 <= nkeys <= 4; key column i of the probe side pairs with key column i of the build side, and the two must have
+ * the same type (any of the five).  Equality is the engine's `=`: Double.equals for DOUBLE, so every NaN is
+ * one value and -0.0 != 0.0.  STRING keys compare by string, not by code: the sides may carry different dictionaries, and a
+ * probe string the build dictionary does not hold matches nothing.  A row with a NULL in ANY key column matches nothing,
+ * on either side.  A shared hash is never taken for a match: every key image is compared.
+ *
+ * Rows and order: that of a nested loop with the probe side outside, deterministic -- the same inputs give the same bytes
+ * on every run and every context; nothing depends on the order in which atomics arrive.
+ *   QE_JOIN_INNER  one row per (probe row, matching build row), in probe-row order and inside one probe row in build-row order
+ *   QE_JOIN_LEFT   the same, plus one row for every probe row without a match, in its place, every build column NULL
+ *   QE_JOIN_SEMI   every probe row with at least one match, once, in probe order
+ *   QE_JOIN_ANTI   every probe row without a match (a NULL key is no match), in probe order
+ * SEMI and ANTI take no build columns (nbuild_out == 0).
+ *
+ * Columns: the listed probe columns, then the listed build columns; a column may be listed twice, a list may be empty,
+ * but there must be at least one output column.  A STRING column carries its source's dictionary; nullability is that of
+ * the source, and under LEFT every build column is nullable (an unmatched row: validity 0, value zero).  The result has
+ * the layouts of every other result: qe_result_order_by_keys, qe_result_to_host, qe_result_concat, qe_gather take it.
+ *
+ * Lifetime: the table reads the build side's columns again at probe time, so the build input must outlive the table; the
+ * table keeps the dictionaries alive and may be probed any number of times.
+ *
+ * Errors (*out = NULL): QE_ERR_INVALID_ARG for a null pointer, both or neither member of a qe_join_input set, a column out
+ * of range, paired key columns of different types, nkeys outside 1..4, a schema-only batch, an unknown join type, no
+ * output column, build columns with SEMI / ANTI; QE_ERR_UNSUPPORTED for a side of more than 2^32 - 2 rows (rows are
+ * uint32 with one sentinel, as in the sort); QE_ERR_HIP on a planning-only context; QE_ERR_OOM when the output does not
+ * fit.  Output counts and offsets are 64-bit throughout.
+ * Known limit: the matches of ONE probe row are walked by one lane, so a probe key with very many matches is slow. */
+enum { QE_JOIN_INNER = 0, QE_JOIN_LEFT = 1, QE_JOIN_SEMI = 2, QE_JOIN_ANTI = 3 };
+/* one side of a join: exactly one of the two is non-NULL */
+typedef struct { const qe_result *result; const qe_batch *batch; } qe_join_input;
+typedef struct qe_join_table qe_join_table;
+
+int32_t qe_join_build(qe_ctx *ctx, const qe_join_input *build, const int32_t *key_cols, int32_t nkeys,
+                      qe_join_table **out);
+int64_t qe_join_table_rows(const qe_join_table *table);      /* build rows whose key holds no NULL */
+void    qe_join_table_free(qe_ctx *ctx, qe_join_table *table);
+int32_t qe_join_probe(qe_ctx *ctx, const qe_join_table *table, const qe_join_input *probe,
+                      const int32_t *key_cols, int32_t nkeys, int32_t join_type,
+                      const int32_t *probe_out_cols, int32_t nprobe_out,
+                      const int32_t *build_out_cols, int32_t nbuild_out, qe_result **out);
+/* what the last qe_join_build / qe_join_probe of this context did: out[0] build rows in the table, out[1] probe rows,
+ * out[2] output rows, out[3] longest candidate run one probe row scanned */
+int32_t qe_ctx_last_join_stats(const qe_ctx *ctx, int64_t out[4]);
+
+/* zero-copy: a batch whose columns ARE the result's (not owned; the result must outlive the batch).  Same columns, same
+ * validity (NULL where the result has none), same dictionaries, nrows = the result's count (zero rows: a zero-row batch).
+ * The batch goes into qe_filter_project / qe_filter_aggregate / qe_filter_groupby like any other: that is how a join is
+ * followed by a GROUP BY, a filter (HAVING) or a projection without leaving HBM.  qe_batch_free frees only the handle.  A
+ * qe_result_free that comes while such a batch is alive does not pull the buffers from under it: they are released when
+ * the result's last batch is freed (the result handle itself must not be used after qe_result_free all the same). */
+int32_t qe_batch_from_result(qe_ctx *ctx, const qe_result *result, qe_batch **out);
+
 /* ---- the exchange step of a row-range sharded scan -------------------------------------------------------
  * One process (one qe_ctx) per GPU; rank r scans rows [r*N/P, (r+1)*N/P) with NO communication.  Only a plan whose root
  * materialises its result on one rank (evaluator/Planner.kt:30-63: ONE Operator yields the whole result; Main.kt:18

@@ -55,6 +55,18 @@ internal object QeNative {
     // compareBy().thenByDescending() on a stable sort, LIMIT as a top-k selection on the device
     val qe_result_order_by_keys = handle("qe_result_order_by_keys", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_LONG, ADDRESS)
 
+    // ---- hash equi-join of two device-resident sides; a side is a qe_join_input {qe_result*, qe_batch*}, exactly one set ----
+    // ctx, build side, int key_cols[nkeys], nkeys (1..4), qe_join_table** -> status; the build side must outlive the table
+    val qe_join_build = handle("qe_join_build", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, ADDRESS)
+    val qe_join_table_rows = handle("qe_join_table_rows", JAVA_LONG, ADDRESS)                         // build rows with a key
+    val qe_join_table_free = handle("qe_join_table_free", null, ADDRESS, ADDRESS)
+    // ctx, table, probe side, int key_cols[nkeys], nkeys, join type (0 INNER, 1 LEFT, 2 SEMI, 3 ANTI), int probe_out[n], n,
+    // int build_out[m], m (0 for SEMI / ANTI), qe_result** -> status: rows in nested-loop order, probe side outside
+    val qe_join_probe = handle("qe_join_probe", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS)
+    val qe_ctx_last_join_stats = handle("qe_ctx_last_join_stats", JAVA_INT, ADDRESS, ADDRESS)         // ctx, long[4]
+    // ctx, result, qe_batch** -> status: a batch whose columns ARE the result's (zero copy): the input of the next plan
+    val qe_batch_from_result = handle("qe_batch_from_result", JAVA_INT, ADDRESS, ADDRESS, ADDRESS)
+
     // ---- the exchange step of a row-range sharded scan: one JVM process (one qe_ctx) per GPU ----
     // rank 0: qe_comm_unique_id(ctx, id128) -> the 128 bytes travel to the other ranks over the host's own channel
     val qe_comm_unique_id = handle("qe_comm_unique_id", JAVA_INT, ADDRESS, ADDRESS)

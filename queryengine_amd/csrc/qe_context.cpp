@@ -131,6 +131,8 @@ void free_batch(qe_ctx *ctx, qe_batch *b) {
             ctx->pool.release(c.data);
             ctx->pool.release(c.validity);
         }
+    if (qe_result *r = b->view_of)   // a view of a result: the last one to go releases a result that was freed meanwhile
+        if (--r->views == 0 && r->free_pending) free_result(ctx, r);
     delete b;
 }
 

@@ -3,6 +3,7 @@
 //   qe_api.cpp       plan cache + geometry (get_plan), the filter+project executor and its entry points
 //   qe_groupby.cpp   the global aggregate and the GROUP BY routes with their entry points
 //   qe_result.cpp    results on the device and their way to the host
+//   qe_join.cpp      the hash equi-join of two device-resident sides, a result as the next plan's batch
 #pragma once
 
 #include <memory>

@@ -168,6 +168,7 @@ struct qe_batch {
     int64_t nrows = 0;
     bool schema_only = false;
     std::vector<qe::Column> cols;
+    struct qe_result *view_of = nullptr;   // qe_batch_from_result: the result whose buffers the columns are
 };
 
 struct qe_expr {
@@ -195,6 +196,8 @@ struct qe_result {
     int64_t count = 0;
     int64_t capacity = 0;
     std::vector<qe::OutColumn> cols;
+    int views = 0;            // batches made by qe_batch_from_result that are still alive
+    bool free_pending = false;// qe_result_free came while views > 0: the last view's qe_batch_free releases the buffers
 };
 
 namespace qe {
@@ -426,6 +429,7 @@ struct qe_ctx {
     std::vector<struct qe_host_result *> host_results;   // alive host results (their copies may still read a qe_result)
     qe_csv_device_stats csv_stats{};   // what the last qe_csv_parse*_device call did
     int64_t sort_stats[4] = {0, 0, 0, 0};   // qe_ctx_last_sort_stats: path, rows sorted, radix passes, selection passes
+    int64_t join_stats[4] = {0, 0, 0, 0};   // qe_ctx_last_join_stats: build rows in the table, probe rows, output rows, longest run walked
 };
 
 struct qe_host_result {

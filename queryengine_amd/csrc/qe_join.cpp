@@ -1,0 +1,321 @@
+// qe_join.cpp -- host side of the hash equi-join (kernels: qe_join.hip) and qe_batch_from_result, the way a
+// result goes into the next plan without leaving HBM.
+#include <algorithm>
+#include <cstdlib>
+#include <functional>
+
+#include "qe_exec.h"
+#include "qe_kernels.h"
+
+namespace qe {
+namespace {
+
+constexpr int64_t kMaxSideRows = (1ll << 32) - 2;   // rows are uint32 with one sentinel
+constexpr int kMaxDirBits = 26;                     // 64 Mi buckets: the directory stays at 256 MiB
+
+// one side of a join, whichever of the two it is: columns and a row count
+struct SideCol {
+    int type = 0;
+    const void *data = nullptr;
+    const uint64_t *validity = nullptr;
+    std::shared_ptr<DictData> dict;
+};
+struct Side {
+    int64_t nrows = 0;
+    std::vector<SideCol> cols;
+};
+
+Side side_of(const qe_join_input *in, const char *who) {
+    if (!in || (in->result != nullptr) == (in->batch != nullptr))
+        fail(QE_ERR_INVALID_ARG, std::string(who) + ": exactly one of qe_join_input.result and .batch must be set");
+    Side s;
+    if (in->result) {
+        s.nrows = in->result->count;
+        for (const OutColumn &c : in->result->cols) s.cols.push_back({c.type, c.data, c.validity, c.dict});
+    } else {
+        if (in->batch->schema_only) fail(QE_ERR_INVALID_ARG, std::string(who) + ": a schema-only batch has no rows to join");
+        s.nrows = in->batch->nrows;
+        for (const Column &c : in->batch->cols) s.cols.push_back({c.type, c.data, c.validity, c.dict});
+    }
+    for (const SideCol &c : s.cols)
+        if (c.type == QE_STRING && !c.dict) fail(QE_ERR_INVALID_ARG, std::string(who) + ": STRING column without dictionary");
+    return s;
+}
+
+void check_cols(const Side &s, const int32_t *cols, int32_t n, const char *who, const char *what) {
+    if (n < 0 || (n > 0 && !cols)) fail(QE_ERR_INVALID_ARG, std::string(who) + ": bad " + what + " list");
+    for (int32_t i = 0; i < n; i++)
+        if (cols[i] < 0 || cols[i] >= (int32_t)s.cols.size()) fail(QE_ERR_INVALID_ARG, std::string(who) + ": " + what + " column out of range");
+}
+
+uint64_t hash_mask_from_env() {
+    // test switch: keep only the low n bits of the hash, so that many keys share one
+    if (const char *e = std::getenv("QE_JOIN_HASH_BITS")) {
+        const int n = std::atoi(e);
+        if (n >= 0 && n < 64) return n == 0 ? 0ull : (~0ull >> (64 - n));
+    }
+    return ~0ull;
+}
+
+}  // namespace
+}  // namespace qe
+
+struct qe_join_table {
+    qe::Side build;                 // the build input's columns (read again by the gathers of a probe) + its dictionaries
+    std::vector<int32_t> key_cols;
+    int64_t m = 0;                  // build rows with a key
+    int dbits = 4;
+    uint64_t mask = ~0ull;
+    uint32_t *dir = nullptr;        // 2^dbits + 1 bucket offsets
+    uint32_t *rows = nullptr;       // build row per sorted entry
+    unsigned long long *img[4] = {nullptr, nullptr, nullptr, nullptr};   // key images per sorted entry
+};
+
+namespace qe {
+namespace {
+
+void free_table(qe_ctx *ctx, qe_join_table *t) {
+    if (!t) return;
+    ctx->pool.release(t->dir);
+    ctx->pool.release(t->rows);
+    for (auto *p : t->img) ctx->pool.release(p);
+    delete t;
+}
+
+// key columns of `side` as the kernels read them.  STRING keys go through a code -> canonical BUILD code table made here
+// from the two dictionaries (-1: the build dictionary does not hold the string; a dictionary that lists a string twice
+// maps both codes to the first): `tables` keeps the host copies alive until the uploads have completed.
+JoinKeyCols key_columns(qe_ctx *ctx, PoolScratch &sc, const Side &side, const int32_t *cols, int32_t nkeys, const Side &build,
+                        const std::vector<int32_t> &build_cols, std::vector<std::vector<int32_t>> &tables) {
+    JoinKeyCols kc{};
+    kc.nkeys = nkeys;
+    tables.reserve((size_t)nkeys);
+    for (int32_t k = 0; k < nkeys; k++) {
+        const SideCol &c = side.cols[(size_t)cols[k]];
+        kc.type[k] = c.type;
+        kc.data[k] = c.data;
+        kc.validity[k] = (const unsigned long long *)c.validity;
+        if (c.type != QE_STRING) continue;
+        const DictData &bd = *build.cols[(size_t)build_cols[(size_t)k]].dict;
+        kc.ncodes[k] = (int)c.dict->entries.size();
+        if (c.dict.get() == &bd && bd.index.size() == bd.entries.size()) continue;   // the build dictionary itself, no duplicates: codes as they are
+        std::vector<int32_t> table(c.dict->entries.size());
+        for (size_t i = 0; i < table.size(); i++) table[i] = bd.find(c.dict->entries[i]);
+        int *d = (int *)sc.alloc(std::max<size_t>(table.size() * 4, 16));
+        tables.push_back(std::move(table));
+        if (!tables.back().empty())
+            QE_HIP(hipMemcpyAsync(d, tables.back().data(), tables.back().size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        kc.remap[k] = d;
+    }
+    return kc;
+}
+
+qe_join_table *build_table(qe_ctx *ctx, const qe_join_input *in, const int32_t *key_cols, int32_t nkeys) {
+    const char *who = "qe_join_build";
+    Side side = side_of(in, who);
+    if (nkeys < 1 || nkeys > 4 || !key_cols) fail(QE_ERR_INVALID_ARG, std::string(who) + ": 1 <= nkeys <= 4");
+    check_cols(side, key_cols, nkeys, who, "key");
+    if (side.nrows > kMaxSideRows) fail(QE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 2 rows");
+    need_device(ctx);
+
+    std::unique_ptr<qe_join_table, std::function<void(qe_join_table *)>> t(new qe_join_table(), [ctx](qe_join_table *p) { free_table(ctx, p); });
+    t->build = std::move(side);
+    t->key_cols.assign(key_cols, key_cols + nkeys);
+    t->mask = hash_mask_from_env();
+    const int64_t n = t->build.nrows;
+
+    PoolScratch sc(ctx);
+    std::vector<std::vector<int32_t>> tables;
+    JoinBuildArgs ba{};
+    ba.kc = key_columns(ctx, sc, t->build, key_cols, nkeys, t->build, t->key_cols, tables);
+    ba.n = n;
+    ba.mask = t->mask;
+    unsigned long long *kbuf[2] = {(unsigned long long *)sc.alloc(std::max<size_t>((size_t)n * 8, 16)), (unsigned long long *)sc.alloc(std::max<size_t>((size_t)n * 8, 16))};
+    uint32_t *rbuf[2] = {(uint32_t *)sc.alloc(std::max<size_t>((size_t)n * 4, 16)), (uint32_t *)sc.alloc(std::max<size_t>((size_t)n * 4, 16))};
+    unsigned long long *img[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < nkeys; k++) img[k] = ba.img[k] = (unsigned long long *)sc.alloc(std::max<size_t>((size_t)n * 8, 16));
+    ba.hash = kbuf[0];
+    ba.rows = rbuf[0];
+    ba.valid_words = (unsigned long long *)sc.alloc(std::max<size_t>(bitmap_bytes(n), 16));
+    ba.nvalid = (unsigned long long *)sc.alloc(16);
+    QE_HIP(hipMemsetAsync(ba.nvalid, 0, 16, ctx->stream));
+    launch_join_build_keys(ctx->stream, ba);
+    unsigned long long m = 0;
+    QE_HIP(hipMemcpyAsync(&m, ba.nvalid, 8, hipMemcpyDeviceToHost, ctx->stream));
+    QE_HIP(hipGetLastError());
+    QE_HIP(hipStreamSynchronize(ctx->stream));   // (also: the code tables are on the device now)
+    if ((int64_t)m > n) fail(QE_ERR_INTERNAL, std::string(who) + ": counted more keyed rows than rows");
+    t->m = (int64_t)m;
+
+    // directory over the top hash bits: about one bucket per keyed row
+    int dbits = 4;
+    while (dbits < kMaxDirBits && (1ll << dbits) < t->m) dbits++;
+    t->dbits = dbits;
+
+    // stable LSD radix sort of (hash, row) on the digits that cover the directory bits; then the rows without a key go
+    // behind the others (one pass on their bit).  Entries with equal hashes (so: equal keys) stay in build-row order.
+    int cur = 0;
+    if (n > 0) {
+        uint32_t *hist = (uint32_t *)sc.alloc((size_t)((n + 1023) / 1024) * 16 * 4);
+        const int ndigits = (dbits + 3) / 4;
+        for (int shift = 64 - 4 * ndigits; shift < 64; shift += 4) {
+            launch_radix_pass(ctx->stream, kbuf[cur], rbuf[cur], nullptr, n, shift, hist, kbuf[cur ^ 1], rbuf[cur ^ 1]);
+            cur ^= 1;
+        }
+        if (t->m < n) {
+            launch_radix_pass(ctx->stream, kbuf[cur], rbuf[cur], (const uint64_t *)ba.valid_words, n, 65, hist, kbuf[cur ^ 1], rbuf[cur ^ 1]);
+            cur ^= 1;
+        }
+    }
+    t->dir = (uint32_t *)ctx->pool.alloc(((size_t)1 << dbits) * 4 + 16);
+    launch_join_directory(ctx->stream, kbuf[cur], t->m, dbits, t->dir);
+    t->rows = (uint32_t *)ctx->pool.alloc(std::max<size_t>((size_t)t->m * 4, 16));
+    if (t->m > 0) QE_HIP(hipMemcpyAsync(t->rows, rbuf[cur], (size_t)t->m * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    for (int k = 0; k < nkeys; k++) {
+        t->img[k] = (unsigned long long *)ctx->pool.alloc(std::max<size_t>((size_t)t->m * 8, 16));
+        launch_gather_rows(ctx->stream, 8, img[k], rbuf[cur], t->m, t->img[k]);
+    }
+    QE_HIP(hipGetLastError());
+    QE_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->join_stats[0] = t->m;
+    ctx->join_stats[1] = ctx->join_stats[2] = ctx->join_stats[3] = 0;
+    return t.release();
+}
+
+qe_result *probe_table(qe_ctx *ctx, const qe_join_table *t, const qe_join_input *in, const int32_t *key_cols, int32_t nkeys, int32_t join_type,
+                       const int32_t *probe_out, int32_t nprobe_out, const int32_t *build_out, int32_t nbuild_out) {
+    const char *who = "qe_join_probe";
+    const Side side = side_of(in, who);
+    if (!key_cols || nkeys != (int32_t)t->key_cols.size()) fail(QE_ERR_INVALID_ARG, std::string(who) + ": nkeys differs from the table's");
+    if (join_type < QE_JOIN_INNER || join_type > QE_JOIN_ANTI) fail(QE_ERR_INVALID_ARG, std::string(who) + ": unknown join type");
+    check_cols(side, key_cols, nkeys, who, "key");
+    for (int32_t k = 0; k < nkeys; k++)
+        if (side.cols[(size_t)key_cols[k]].type != t->build.cols[(size_t)t->key_cols[(size_t)k]].type)
+            fail(QE_ERR_INVALID_ARG, std::string(who) + ": key column " + std::to_string(k) + " is " + type_name(side.cols[(size_t)key_cols[k]].type) +
+                                         " on the probe side and " + type_name(t->build.cols[(size_t)t->key_cols[(size_t)k]].type) + " on the build side");
+    check_cols(side, probe_out, nprobe_out, who, "probe output");
+    check_cols(t->build, build_out, nbuild_out, who, "build output");
+    const bool pairs = join_type == QE_JOIN_INNER || join_type == QE_JOIN_LEFT;
+    if (!pairs && nbuild_out != 0) fail(QE_ERR_INVALID_ARG, std::string(who) + ": a SEMI / ANTI join has no build columns");
+    if (nprobe_out + nbuild_out < 1) fail(QE_ERR_INVALID_ARG, std::string(who) + ": no output column");
+    if (side.nrows > kMaxSideRows) fail(QE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 2 rows");
+    need_device(ctx);
+
+    const int64_t n = side.nrows;
+    PoolScratch sc(ctx);
+    std::vector<std::vector<int32_t>> tables;
+    JoinProbeArgs pa{};
+    pa.kc = key_columns(ctx, sc, side, key_cols, nkeys, t->build, t->key_cols, tables);
+    pa.t.dir = t->dir;
+    pa.t.rows = t->rows;
+    for (int k = 0; k < 4; k++) pa.t.img[k] = t->img[k];
+    pa.t.dbits = t->dbits;
+    pa.t.nkeys = nkeys;
+    pa.t.mask = t->mask;
+    pa.n = n;
+    pa.join_type = join_type;
+    const int64_t nblocks = join_probe_blocks(n);
+    pa.cnt = (uint32_t *)sc.alloc(std::max<size_t>((size_t)n * 4, 16));
+    if (pairs) pa.first = (uint32_t *)sc.alloc(std::max<size_t>((size_t)n * 4, 16));
+    pa.blocksum = (unsigned long long *)sc.alloc(std::max<size_t>((size_t)nblocks * 8, 16));
+    unsigned long long *d_ctl = (unsigned long long *)sc.alloc(16);   // [0] total, [1] longest walk (u32)
+    pa.longest = (uint32_t *)(d_ctl + 1);
+    QE_HIP(hipMemsetAsync(d_ctl, 0, 16, ctx->stream));
+    launch_join_count(ctx->stream, pa);
+    launch_join_scan(ctx->stream, pa.blocksum, nblocks, d_ctl);
+    unsigned long long h_ctl[2] = {0, 0};
+    QE_HIP(hipMemcpyAsync(h_ctl, d_ctl, 16, hipMemcpyDeviceToHost, ctx->stream));   // the one read-back: the output's size
+    QE_HIP(hipGetLastError());
+    QE_HIP(hipStreamSynchronize(ctx->stream));
+    const int64_t total = (int64_t)h_ctl[0];   // at most 2^32 rows of at most 2^32 matches: fits; an output too large for the
+                                               // device is reported by the pool below (QE_ERR_OOM)
+
+    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [ctx](qe_result *r) { free_result(ctx, r); });
+    res->count = res->capacity = total;
+    pa.total = (unsigned long long)total;
+    pa.prow_out = (uint32_t *)sc.alloc(std::max<size_t>((size_t)total * 4, 16));
+    if (pairs) pa.brow_out = (uint32_t *)sc.alloc(std::max<size_t>((size_t)total * 4, 16));
+    launch_join_write(ctx->stream, pa);
+
+    auto emit = [&](const SideCol &src, const uint32_t *rows, bool force_nullable) {
+        res->cols.emplace_back();
+        OutColumn &oc = res->cols.back();
+        oc.type = src.type;
+        oc.dict = src.dict;
+        oc.dict_handle.d = src.dict;
+        oc.nullable = force_nullable || src.validity != nullptr;
+        oc.data = ctx->pool.alloc(std::max<size_t>(column_bytes(src.type, total), 16));
+        if (oc.nullable) oc.validity = (uint64_t *)ctx->pool.alloc(std::max<size_t>(bitmap_bytes(total), 16));
+        if (src.type == QE_BOOLEAN) launch_join_gather_bits(ctx->stream, (const uint64_t *)src.data, rows, total, (uint64_t *)oc.data);
+        else launch_join_gather(ctx->stream, (int)type_width(src.type), src.data, rows, total, oc.data);
+        if (oc.nullable) launch_join_gather_bits(ctx->stream, src.validity, rows, total, oc.validity);
+    };
+    for (int32_t i = 0; i < nprobe_out; i++) emit(side.cols[(size_t)probe_out[i]], pa.prow_out, false);
+    for (int32_t i = 0; i < nbuild_out; i++) emit(t->build.cols[(size_t)build_out[i]], pa.brow_out, join_type == QE_JOIN_LEFT);
+    QE_HIP(hipGetLastError());
+    QE_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->join_stats[0] = t->m;
+    ctx->join_stats[1] = n;
+    ctx->join_stats[2] = total;
+    ctx->join_stats[3] = (int64_t)(uint32_t)h_ctl[1];
+    return res.release();
+}
+
+}  // namespace
+}  // namespace qe
+
+using namespace qe;
+
+extern "C" {
+
+int32_t qe_join_build(qe_ctx *ctx, const qe_join_input *build, const int32_t *key_cols, int32_t nkeys, qe_join_table **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !build || !key_cols || !out) return QE_ERR_INVALID_ARG;
+    return guarded(ctx, [&] { *out = build_table(ctx, build, key_cols, nkeys); });
+}
+
+int64_t qe_join_table_rows(const qe_join_table *table) { return table ? table->m : -1; }
+
+void qe_join_table_free(qe_ctx *ctx, qe_join_table *table) {
+    if (!ctx || !table) return;
+    free_table(ctx, table);
+}
+
+int32_t qe_join_probe(qe_ctx *ctx, const qe_join_table *table, const qe_join_input *probe, const int32_t *key_cols, int32_t nkeys, int32_t join_type,
+                      const int32_t *probe_out_cols, int32_t nprobe_out, const int32_t *build_out_cols, int32_t nbuild_out, qe_result **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !table || !probe || !key_cols || !out) return QE_ERR_INVALID_ARG;
+    return guarded(ctx, [&] {
+        *out = probe_table(ctx, table, probe, key_cols, nkeys, join_type, probe_out_cols, nprobe_out, build_out_cols, nbuild_out);
+    });
+}
+
+int32_t qe_ctx_last_join_stats(const qe_ctx *ctx, int64_t out[4]) {
+    if (!ctx || !out) return QE_ERR_INVALID_ARG;
+    for (int i = 0; i < 4; i++) out[i] = ctx->join_stats[i];
+    return QE_OK;
+}
+
+int32_t qe_batch_from_result(qe_ctx *ctx, const qe_result *result, qe_batch **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !result || !out) return QE_ERR_INVALID_ARG;
+    return guarded(ctx, [&] {
+        std::unique_ptr<qe_batch> b(new qe_batch());
+        b->nrows = result->count;
+        for (const OutColumn &c : result->cols) {
+            Column col;
+            col.type = c.type;
+            col.data = c.data;
+            col.validity = c.validity;
+            col.dict = c.dict;
+            col.owned = false;
+            b->cols.push_back(col);
+        }
+        // the batch reads the result's buffers: a qe_result_free that comes before the batch's is deferred (free_batch)
+        b->view_of = const_cast<qe_result *>(result);
+        b->view_of->views++;
+        *out = b.release();
+    });
+}
+
+}  // extern "C"

@@ -92,6 +92,59 @@ void launch_select_compact(hipStream_t s, const unsigned long long *keys, int64_
 void launch_gather_rows(hipStream_t s, int width, const void *src, const uint32_t *rows, int64_t n, void *out);
 void launch_gather_bits_rows(hipStream_t s, const uint64_t *src, const uint32_t *rows, int64_t n, uint64_t *out);
 
+// ---- hash equi-join (qe_join.hip) ----
+// the key columns of one side; the image of a key column is the u64 two equal values share
+struct JoinKeyCols {
+    int nkeys;
+    int type[4];                            // QE_* of the key columns
+    const void *data[4];
+    const unsigned long long *validity[4];  // or null
+    const int *remap[4];                    // QE_STRING: code -> canonical code in the BUILD dictionary (-1: not there); null = the code itself
+    int ncodes[4];                          // QE_STRING: entries of the column's dictionary (a code outside matches nothing)
+};
+// build: hash[i], rows[i] = i and img[k][i] of every row, bit i of valid_words = the key holds no NULL, *nvalid += such rows
+struct JoinBuildArgs {
+    JoinKeyCols kc;
+    long long n;
+    unsigned long long mask;                // bits of the hash that are kept ($QE_JOIN_HASH_BITS)
+    unsigned long long *hash;
+    unsigned int *rows;
+    unsigned long long *img[4];
+    unsigned long long *valid_words;
+    unsigned long long *nvalid;
+};
+void launch_join_build_keys(hipStream_t s, const JoinBuildArgs &a);
+// dir[b] = first of the m sorted entries whose top dbits hash bits are >= b; 2^dbits + 1 entries
+void launch_join_directory(hipStream_t s, const unsigned long long *sorted_hash, int64_t m, int dbits, uint32_t *dir);
+// the table as the probe sees it: entries sorted by bucket, inside a bucket in build-row order
+struct JoinTableView {
+    const unsigned int *dir;
+    const unsigned int *rows;               // build row of sorted entry s
+    const unsigned long long *img[4];       // its key images
+    int dbits, nkeys;
+    unsigned long long mask;
+};
+struct JoinProbeArgs {
+    JoinKeyCols kc;
+    JoinTableView t;
+    long long n;                            // probe rows
+    int join_type;                          // QE_JOIN_*
+    unsigned int *cnt;                      // output rows of probe row i
+    unsigned int *first;                    // sorted entry of its first match (0xFFFFFFFF: none); null for SEMI / ANTI
+    unsigned long long *blocksum;           // per block of 256 probe rows: pass 1 writes the sum, launch_join_scan the offset
+    unsigned int *longest;                  // max over the probe rows of the entries one row walked
+    unsigned long long total;               // pass 2: pairs the lists hold
+    unsigned int *prow_out, *brow_out;      // pass 2: the pairs (brow_out null for SEMI / ANTI; build row 0xFFFFFFFF = none)
+};
+int64_t join_probe_blocks(int64_t n);       // entries of blocksum
+void launch_join_count(hipStream_t s, const JoinProbeArgs &a);
+void launch_join_scan(hipStream_t s, unsigned long long *blocksum, int64_t nblocks, unsigned long long *total);
+void launch_join_write(hipStream_t s, const JoinProbeArgs &a);
+// out[j] = src[rows[j]], or zero for row 0xFFFFFFFF; width 4 or 8
+void launch_join_gather(hipStream_t s, int width, const void *src, const uint32_t *rows, int64_t n, void *out);
+// bit j of out = bit rows[j] of src (src null: 1), 0 for row 0xFFFFFFFF; whole words are written
+void launch_join_gather_bits(hipStream_t s, const uint64_t *src, const uint32_t *rows, int64_t n, uint64_t *out);
+
 // place nbits bits of src at bit offset dst_bit_offset of dst (bitmap words; concatenation of results / gather)
 void launch_bitmap_place(hipStream_t s, uint64_t *dst, int64_t dst_bit_offset, const uint64_t *src, int64_t nbits);
 

@@ -204,6 +204,10 @@ void qe_result_free(qe_ctx *ctx, qe_result *r) {
             h->waited = true;
             h->src = nullptr;
         }
+    if (r && r->views > 0) {   // a batch of qe_batch_from_result still reads the buffers: its qe_batch_free releases them
+        r->free_pending = true;
+        return;
+    }
     free_result(ctx, r);
 }
 

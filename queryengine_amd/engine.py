@@ -166,6 +166,17 @@ class Context:
         return {"path": "select" if out[0] == 1 else "sort", "sorted_rows": int(out[1]), "radix_passes": int(out[2]),
                 "select_passes": int(out[3])}
 
+    def join_build(self, side, key_cols: Sequence[int]) -> "JoinTable":
+        """qe_join_build: the hash table of an equi-join over the key columns of `side` (a Result or a DeviceBatch)."""
+        return JoinTable(self, side, key_cols)
+
+    def last_join_stats(self) -> List[int]:
+        """qe_ctx_last_join_stats: [build rows in the table, probe rows, output rows, longest candidate run one probe row
+        scanned] of the last join_build / probe on this context."""
+        out = (C.c_int64 * 4)()
+        N.check(self.handle, self._lib.qe_ctx_last_join_stats(self.handle, out))
+        return [int(v) for v in out]
+
     def concat(self, parts: Sequence["Result"]) -> "Result":
         """qe_result_concat: results of this device, concatenated in the given order."""
         arr = (C.c_void_p * max(1, len(parts)))(*[p.handle for p in parts])
@@ -295,6 +306,61 @@ class DeviceBatch:
             pass
 
 
+def _join_input(side) -> N.JoinInput:
+    """A Result or a DeviceBatch as a qe_join_input."""
+    if isinstance(side, Result):
+        return N.JoinInput(side.handle, None)
+    if isinstance(side, DeviceBatch):
+        return N.JoinInput(None, side.handle)
+    raise TypeError("a join side is a Result or a DeviceBatch")
+
+
+def _i32_array(values: Sequence[int]):
+    return (C.c_int32 * max(1, len(values)))(*[int(v) for v in values])
+
+
+class JoinTable:
+    """qe_join_table: the build side of a hash equi-join, probed any number of times.  Keeps the build side alive (the
+    table reads its columns again at probe time)."""
+
+    def __init__(self, ctx: Context, side, key_cols: Sequence[int]):
+        self.ctx = ctx
+        self.side = side
+        self.key_cols = [int(c) for c in key_cols]
+        self.handle = None
+        h = C.c_void_p()
+        inp = _join_input(side)
+        N.check(ctx.handle, ctx._lib.qe_join_build(ctx.handle, C.byref(inp), _i32_array(self.key_cols), len(self.key_cols), C.byref(h)))
+        self.handle = h
+
+    @property
+    def rows(self) -> int:
+        """qe_join_table_rows: build rows whose key holds no NULL."""
+        return int(self.ctx._lib.qe_join_table_rows(self.handle))
+
+    def probe(self, side, key_cols: Sequence[int], join_type: int = N.JOIN_INNER, probe_out: Sequence[int] = (),
+              build_out: Sequence[int] = ()) -> "Result":
+        """qe_join_probe: the listed probe columns, then the listed build columns, in nested-loop order (probe outside)."""
+        h = C.c_void_p()
+        inp = _join_input(side)
+        N.check(self.ctx.handle, self.ctx._lib.qe_join_probe(
+            self.ctx.handle, self.handle, C.byref(inp), _i32_array(key_cols), len(key_cols), int(join_type),
+            _i32_array(probe_out), len(probe_out), _i32_array(build_out), len(build_out), C.byref(h)))
+        return Result(self.ctx, h)
+
+    def free(self) -> None:
+        if self.handle and self.ctx.handle:
+            self.ctx._lib.qe_join_table_free(self.ctx.handle, self.handle)
+        self.handle = None
+        self.side = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class CompiledExpression:
     """qe_expr: the analogue of the RowCallable returned by compileExpression (Compiler.kt:20-26)."""
 
@@ -362,6 +428,13 @@ class Result:
 
     def to_columns(self) -> List[Column]:
         return [self.column_to_host(i) for i in range(self.ncols)]
+
+    def as_batch(self) -> "DeviceBatch":
+        """qe_batch_from_result: a batch whose columns ARE this result's (zero copy), for the next plan; the batch keeps
+        this result alive."""
+        h = C.c_void_p()
+        N.check(self.ctx.handle, self.ctx._lib.qe_batch_from_result(self.ctx.handle, self.handle, C.byref(h)))
+        return DeviceBatch(self.ctx, h, [self])
 
     def to_host(self) -> "HostResult":
         """qe_result_to_host: START copying every column into pinned host memory owned by the library (copy stream) and

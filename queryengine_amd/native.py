@@ -29,6 +29,7 @@ AGG_MIN, AGG_MAX, AGG_SUM, AGG_COUNT, AGG_AVG = range(5)
 COMM_ID_BYTES = 128
 FORM_RING, FORM_TWO_PASS, FORM_DENSE, FORM_PER_NODE, FORM_NO_FILTER, FORM_LOCAL = range(6)
 FORM_GROUPBY_DENSE, FORM_GROUPBY_HASHED, FORM_GROUPBY_HASH_PARTITIONED = 8, 9, 10
+JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = range(4)
 
 
 class QeError(RuntimeError):
@@ -66,6 +67,11 @@ class CsvDeviceStats(C.Structure):
 class SortKey(C.Structure):
     """qe_sort_key: one ORDER BY key (column 0-based)."""
     _fields_ = [("column", C.c_int32), ("descending", C.c_int32)]
+
+
+class JoinInput(C.Structure):
+    """qe_join_input: one side of a join, a result or a batch (exactly one is set)."""
+    _fields_ = [("result", C.c_void_p), ("batch", C.c_void_p)]
 
 
 # every symbol include/qe_hip.h declares: (name, restype, argtypes)
@@ -132,6 +138,13 @@ SYMBOLS = [
     ("qe_result_order_by", C.c_int32, [_P, _P, C.c_int32, C.POINTER(_P)]),
     ("qe_result_order_by_keys", C.c_int32, [_P, _P, _P, C.c_int32, C.c_int64, C.POINTER(_P)]),
     ("qe_ctx_last_sort_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
+    ("qe_join_build", C.c_int32, [_P, C.POINTER(JoinInput), C.POINTER(C.c_int32), C.c_int32, C.POINTER(_P)]),
+    ("qe_join_table_rows", C.c_int64, [_P]),
+    ("qe_join_table_free", None, [_P, _P]),
+    ("qe_join_probe", C.c_int32, [_P, _P, C.POINTER(JoinInput), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                                  C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_P)]),
+    ("qe_ctx_last_join_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
+    ("qe_batch_from_result", C.c_int32, [_P, _P, C.POINTER(_P)]),
     ("qe_comm_unique_id", C.c_int32, [_P, _P]),
     ("qe_comm_init", C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     ("qe_comm_rank", C.c_int32, [_P]),

@@ -15,6 +15,7 @@ import math
 from typing import Any, Callable, List, Optional, Sequence
 
 from . import engine as E
+from . import native as N
 from .ast import AggregationFunction, Expression
 from .table import Column, ColumnarTable
 
@@ -133,6 +134,137 @@ class OrderByOperator(Operator):
         if self._iter is None:
             raise RuntimeError("Operator not opened")               # OrderByOperator.kt:23
         return next(self._iter, None)
+
+
+def _join_key(values: Sequence[Any]):
+    """The key tuple of a host join, normalised like the device's key images (DESIGN 4 `=`): every NaN is one value, -0.0
+    and 0.0 are two, and a key that holds a ``None`` is no key at all (``None``: the row matches nothing)."""
+    key = []
+    for v in values:
+        if v is None:
+            return None
+        if isinstance(v, float):
+            key.append(("nan",) if v != v else (v, math.copysign(1.0, v)))
+        else:
+            key.append(v)
+    return tuple(key)
+
+
+class HashJoinOperator(Operator):
+    """Equi-join of a probe source against a build source: ``probe_keys[i]`` pairs with ``build_keys[i]`` (column
+    indices).  ``join_type`` is ``native.JOIN_INNER / JOIN_LEFT / JOIN_SEMI / JOIN_ANTI``.  A row is the listed probe
+    columns followed by the listed build columns (``None`` = every column of that side; SEMI and ANTI have no build
+    columns); rows come in the order of a nested loop with the probe side outside: probe-row order, the matches of one
+    probe row in build-row order, an unmatched LEFT row in its place with every build column ``None``.  The reference
+    has no join (Query.g4 reads one table); the operator follows ``OrderByOperator``.
+
+    When both sources are GPU operators of one context (``result()`` and ``ctx``), the join runs on the device
+    (qe_join_build + qe_join_probe) and the operator offers ``result()`` and ``ctx`` itself, so an ``OrderByOperator`` on top
+    sorts in HBM too.  Any other pair of sources is drained and joined on the host with a dict from the key tuple to the
+    list of build rows in order -- the executable statement of the semantics, and the expectation of the device tests."""
+
+    def __init__(self, probe: Operator, build: Operator, probe_keys: Sequence[int], build_keys: Sequence[int],
+                 join_type: int = N.JOIN_INNER, probe_out: Optional[Sequence[int]] = None,
+                 build_out: Optional[Sequence[int]] = None):
+        self.probe, self.build = probe, build
+        self.probe_keys, self.build_keys = [int(c) for c in probe_keys], [int(c) for c in build_keys]
+        if not 1 <= len(self.probe_keys) <= 4 or len(self.probe_keys) != len(self.build_keys):
+            raise ValueError("HashJoinOperator: 1 to 4 key columns, as many on the probe side as on the build side")
+        if join_type not in (N.JOIN_INNER, N.JOIN_LEFT, N.JOIN_SEMI, N.JOIN_ANTI):
+            raise ValueError("HashJoinOperator: unknown join type")
+        self.join_type = join_type
+        self._pairs = join_type in (N.JOIN_INNER, N.JOIN_LEFT)
+        if not self._pairs and build_out:
+            raise ValueError("HashJoinOperator: a SEMI / ANTI join has no build columns")
+        self.probe_out = None if probe_out is None else [int(c) for c in probe_out]
+        self.build_out = None if build_out is None else [int(c) for c in build_out]
+        self._on_device = all(hasattr(s, "result") and hasattr(s, "ctx") for s in (probe, build)) and probe.ctx is build.ctx
+        if self._on_device:
+            self.ctx = probe.ctx
+        self._result: Optional[E.Result] = None
+        self._iter = None
+
+    def _open_device(self) -> None:
+        self.probe.open()
+        try:
+            self.build.open()
+            try:
+                pres, bres = self.probe.result(), self.build.result()
+                probe_out = list(range(pres.ncols)) if self.probe_out is None else self.probe_out
+                build_out = (list(range(bres.ncols)) if self._pairs else []) if self.build_out is None else self.build_out
+                table = self.ctx.join_build(bres, self.build_keys)
+                try:
+                    self._result = table.probe(pres, self.probe_keys, self.join_type, probe_out, build_out)
+                finally:
+                    table.free()
+            finally:
+                self.build.close()
+        finally:
+            self.probe.close()
+
+    def _device_rows(self):
+        cols = self._result.to_columns()       # at the first next(): an operator on top that takes result() never pays it
+        for i in range(len(cols[0]) if cols else 0):
+            yield [c.value(i) for c in cols]
+
+    def _rows_host(self) -> List[List[Any]]:
+        build_rows = mapTo(self.build, [], lambda row: list(row))
+        probe_rows = mapTo(self.probe, [], lambda row: list(row))
+        build_out = self.build_out
+        if build_out is None:
+            if not self._pairs:
+                build_out = []
+            elif build_rows:
+                build_out = list(range(len(build_rows[0])))
+            elif self.join_type == N.JOIN_LEFT and probe_rows:
+                raise ValueError("HashJoinOperator: build_out must be given when a LEFT join's build source yields no row")
+            else:
+                build_out = []
+        table: dict = {}
+        for row in build_rows:
+            key = _join_key([row[c] for c in self.build_keys])
+            if key is not None:
+                table.setdefault(key, []).append(row)
+        out = []
+        for row in probe_rows:
+            head = [row[c] for c in (range(len(row)) if self.probe_out is None else self.probe_out)]
+            key = _join_key([row[c] for c in self.probe_keys])
+            matches = table.get(key, []) if key is not None else []
+            if self.join_type == N.JOIN_SEMI:
+                if matches:
+                    out.append(head)
+            elif self.join_type == N.JOIN_ANTI:
+                if not matches:
+                    out.append(head)
+            elif matches:
+                out.extend(head + [m[c] for c in build_out] for m in matches)
+            elif self.join_type == N.JOIN_LEFT:
+                out.append(head + [None] * len(build_out))
+        return out
+
+    def open(self) -> None:
+        if self._on_device:
+            self._open_device()
+            self._iter = self._device_rows()
+        else:
+            self._iter = iter(self._rows_host())
+
+    def result(self) -> E.Result:
+        """The joined columns in HBM (valid until close()); only when the join ran on the device."""
+        if self._result is None:
+            raise RuntimeError("Operator not initialized")
+        return self._result
+
+    def next(self) -> Optional[List[Any]]:
+        if self._iter is None:
+            raise RuntimeError("Operator not opened")
+        return next(self._iter, None)
+
+    def close(self) -> None:
+        self._iter = None
+        if self._result is not None:
+            self._result.free()
+            self._result = None
 
 
 class ColumnarScanOperator(Operator):
