@@ -2,8 +2,10 @@
 
 The expectation is always the host branch of ``HashJoinOperator`` over the same columns (a dict from the key tuple to the
 list of build rows, probe side outside).  Every probe side and every build side carries an INT64 row id; the two row-id
-output columns are compared exactly, which pins the pairing AND the order.  A handful of rows (first, last, a few in
-between) are checked in every output column.  Keys come from the special-value pools of test_gpu_order_by_keys.py."""
+output columns are compared exactly, which pins the pairing AND the order.  Every output column is then compared in full
+-- type, dictionary, validity, value, the zeroed value under a LEFT "none" -- with join_reference.expected_columns over
+the host branch's pairs, and a handful of rows (first, last, a few in between) once more through boxed values.  Keys come
+from the special-value pools of test_gpu_order_by_keys.py."""
 import ctypes as C
 import math
 
@@ -11,6 +13,7 @@ import numpy as np
 import pytest
 
 from helpers import Fn, assert_columns_equal, col, fn, num
+from join_reference import assert_join_output, expected_columns, expected_nullable, reference_pairs
 from test_gpu_order_by_keys import DOUBLES, INT64S, STRINGS, Rows, make_key
 from queryengine_amd import AggregationFunction as AF
 from queryengine_amd import Column, ColumnarTable, ColumnExpression, DataType, Field, Schema
@@ -69,13 +72,28 @@ def same(a, b):
     return type(a) is type(b) and a == b
 
 
-def check_result(res, want, pcols, bcols, probe_out, build_out, jt, what=""):
-    """`res` against the pairs `want`: both row-id columns exactly, sample rows in every column.  The row id of a side is
-    found by its position in probe_out / build_out (the column index nkeys of the side)."""
+def side_nullable(side, cols):
+    """Which columns of a join side carry a validity bitmap on the device."""
+    if isinstance(side, E.Result):
+        return [bool(side.view(c).nullable) for c in range(len(cols))]
+    return [c.valid is not None for c in cols]
+
+
+def check_result(res, want, pcols, bcols, probe_out, build_out, jt, what="", sides=None):
+    """`res` against the pairs `want`: both row-id columns exactly, EVERY column in full against expected_columns, sample
+    rows in every column through boxed values.  The row id of a side is found by its position in probe_out / build_out
+    (the column index nkeys of the side).  `sides` = (probe side, build side) as given to the join: checks nullability too."""
     m = len(want)
     assert res.count == m, (what, res.count, m)
     out = res.to_columns()
     assert len(out) == len(probe_out) + len(build_out)
+    prow = np.array([p for p, _ in want], dtype=np.int64)
+    brow = np.array([-1 if b is None else b for _, b in want], dtype=np.int64) if jt in (INNER, LEFT) else np.zeros(0, dtype=np.int64)
+    assert_join_output(out, expected_columns(pcols, bcols, prow, brow, probe_out, build_out, jt), brow if jt in (INNER, LEFT) else None,
+                       len(probe_out), what)
+    if sides is not None:
+        nullable = expected_nullable(side_nullable(sides[0], pcols), side_nullable(sides[1], bcols), probe_out, build_out, jt)
+        assert [bool(res.view(k).nullable) for k in range(len(out))] == nullable, what
     for k, c in enumerate(probe_out):
         src = pcols[c]
         assert out[k].type == src.type
@@ -109,6 +127,8 @@ def run_case(ctx, pcols, bcols, pk, bk, jt, kinds=("batch", "batch"), what=""):
     probe_out = list(range(len(pk), len(pcols))) + [pk[0]]
     build_out = (list(range(len(bk), len(bcols))) + [bk[0]]) if pairs else []
     want = host_pairs(pcols, bcols, pk, bk, jt)
+    prow, brow = reference_pairs(pcols, bcols, pk, bk, jt)                       # the numpy reference agrees on every case here
+    assert prow.tolist() == [p for p, _ in want] and (not pairs or [None if b < 0 else b for b in brow.tolist()] == [b for _, b in want])
     pside, pfree = as_side(ctx, pcols, kinds[0])
     bside, bfree = as_side(ctx, bcols, kinds[1])
     table = ctx.join_build(bside, bk)
@@ -120,7 +140,7 @@ def run_case(ctx, pcols, bcols, pk, bk, jt, kinds=("batch", "batch"), what=""):
         assert table.rows == int(keyed.sum())
         res = table.probe(pside, pk, jt, probe_out, build_out)
         try:
-            check_result(res, want, pcols, bcols, probe_out, build_out, jt, what)
+            check_result(res, want, pcols, bcols, probe_out, build_out, jt, what, (pside, bside))
             st = ctx.last_join_stats()
             assert st[:3] == [table.rows, len(pcols[0]), len(want)], st
         finally:

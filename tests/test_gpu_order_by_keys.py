@@ -180,6 +180,47 @@ def test_top_k_of_distinct_doubles_selects_on_the_device(gpu_ctx):
     res.free(); batch.free()
 
 
+def stable_order(key, desc, limit=None):
+    """Row ids of a nullable INT32 key in the documented order, as a numpy stable argsort: ascending NULL first,
+    descending NULL last, ties in row order."""
+    v = key.data.astype(np.int64)
+    valid = key.valid if key.valid is not None else np.ones(len(v), dtype=bool)
+    image = np.where(valid, -v if desc else v, 2 ** 40 if desc else -2 ** 40)
+    order = np.argsort(image, kind="stable")
+    return order if limit is None else order[:limit]
+
+
+@pytest.mark.parametrize("desc", [False, True], ids=["asc", "desc"])
+def test_sort_past_the_grid_cap_is_stable(gpu_ctx, desc):
+    """8192 x 256 + 65 rows: sort_key_kernel, gather_rows_kernel (4 and 8 bytes) and gather_bits_rows_kernel run their
+    stride loops; tens of distinct key values, so stability decides almost every position.  The row-id column and the
+    nullable BOOLEAN column are compared in full."""
+    rng = np.random.default_rng(21)
+    n = 8192 * 256 + 65
+    key = Column(I32, rng.integers(-20, 20, n).astype(np.int32), rng.random(n) >= 0.05)
+    head = Column(I32, key.data[:5000], key.valid[:5000])                        # the numpy order IS the host branch's order
+    for limit in (None, 100):
+        assert stable_order(head, desc, limit).tolist() == host_order([head], [(0, desc)], limit)
+    batch, res, cols = build(gpu_ctx, [key], rng)
+    flag = cols[2]
+    assert flag.valid is not None and len(np.unique(key.data)) == 40
+    for limit in (None, 100):
+        want = stable_order(key, desc, limit)
+        assert want.max() >= 8192 * 256 or limit is not None                     # rows of the second stride take part
+        srt = gpu_ctx.order_by_keys(res, [(0, desc)], limit)
+        try:
+            out = srt.to_columns()
+            assert srt.count == len(want) == (n if limit is None else limit)
+            assert np.array_equal(out[1].data, want), (desc, limit, gpu_ctx.last_sort_stats())
+            for c in (0, 2):                                                     # the key and the flag, every row
+                gv = out[c].valid if out[c].valid is not None else np.ones(len(want), dtype=bool)
+                assert np.array_equal(gv, cols[c].valid[want]), (desc, limit, c)
+                assert np.array_equal(out[c].data[gv], cols[c].data[want][gv]), (desc, limit, c)
+        finally:
+            srt.free()
+    res.free(); batch.free()
+
+
 def test_top_k_across_a_tie(gpu_ctx):
     rng = np.random.default_rng(15)
     n = 300_007
