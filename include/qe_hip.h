@@ -400,6 +400,60 @@ int32_t qe_join_probe(qe_ctx *ctx, const qe_join_table *table, const qe_join_inp
  * out[2] output rows, out[3] longest candidate run one probe row scanned */
 int32_t qe_ctx_last_join_stats(const qe_ctx *ctx, int64_t out[4]);
 
+/* ---- window functions over a result -------------------------------------------------------------------------
+ * The reference has no windows (Query.g4); this is the step that answers a question about a row relative to its neighbours
+ * -- a running total per account, the rank of a row inside its group, the previous value of a series -- without copying the
+ * sorted result to the host.  qe_result_window sorts `result` and appends one column per entry of `fns`.
+ *
+ * Rows and order: the output holds every input row, sorted STABLY by the partition columns ascending, then by `order`, under
+ * the comparator of qe_result_order_by_keys (NULL first ascending, NULL last descending).  npart == 0: the whole input is one
+ * partition; norder == 0: rows keep their input order inside a partition.  Two adjacent rows share a partition when that
+ * comparator returns 0 on every partition column: NULL is a key value, all NaNs are one value, -0.0 != 0.0, STRING compares
+ * by string -- the rule of the group-by keys.  PEERS are rows of one partition that compare 0 on every order key.
+ *
+ * Columns: all input columns first, types, nullability and dictionaries unchanged; then one column per entry of `fns`.
+ *
+ * Frame: always ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW within the partition.  It counts rows, so peers are not
+ * pulled in; whole-partition totals remain group-by + join.
+ *
+ * Functions:
+ *   ROW_NUMBER (1-based), RANK (row number of the first peer), DENSE_RANK: INT64, not nullable; `column` is ignored.
+ *   SUM, MIN, MAX, AVG over a DOUBLE / INT64 / INT32 column: values are converted to double as the group-by aggregates
+ *     convert them; DOUBLE, nullable; NULL inputs are skipped; the value is NULL until the partition has shown its first valid
+ *     value (Accumulators.kt: empty => null).
+ *   COUNT over a column of any type: the valid values so far; DOUBLE, not nullable, like group-by's COUNT.
+ *   Special values follow the rules decided at qe_filter_groupby: a prefix holding a NaN, or both infinities, sums to NaN from
+ *     that row to the partition's end; a prefix of only -0.0 sums to +0.0; MIN / MAX let NaN win and order -0.0 below +0.0.
+ *   LAG / LEAD with 0 <= offset < 2^31 over a column of any type: value and validity of the row `offset` places before /
+ *     after in the same partition; a row beyond the partition's edge gives NULL (validity 0, value zero); always nullable; a
+ *     STRING output carries the source dictionary; offset 0 is the row itself.
+ *
+ * Determinism: the same inputs give the same bytes on every run and on every context.  Every running aggregate is a
+ * fixed-shape scan -- per-tile reduce, one workgroup over the tile aggregates, per-tile downsweep -- in which the values that
+ * are combined depend on the row count and the partition starts alone: no look-back, no result byte depends on the order in
+ * which atomics arrive.
+ *
+ * Numerics: SUM is within gamma_c * sum|x| of the exact prefix sum, c = valid values in the prefix, gamma_c = c*u / (1 - c*u),
+ * u = 2^-53 (the any-order bound stated at qe_filter_groupby); AVG follows the group-by's AVG bound (gamma_(c+1) * sum|x| / c);
+ * integer-valued data below 2^53 comes out exact.
+ *
+ * Errors (*out = NULL): QE_ERR_INVALID_ARG for a null pointer, npart or norder negative, npart + norder > 8, nfn outside
+ * 1..16, a column out of range, an unknown fn, SUM / MIN / MAX / AVG over BOOLEAN or STRING, a negative or too large offset, a
+ * STRING key without a dictionary; QE_ERR_UNSUPPORTED for 2^32 rows or more, as in the sort; QE_ERR_HIP on a planning-only
+ * context; QE_ERR_OOM when the output or the scratch does not fit.  Zero input rows give a zero-row result with the full
+ * output schema. */
+enum { QE_WIN_ROW_NUMBER = 0, QE_WIN_RANK, QE_WIN_DENSE_RANK,
+       QE_WIN_SUM, QE_WIN_COUNT, QE_WIN_MIN, QE_WIN_MAX, QE_WIN_AVG,
+       QE_WIN_LAG, QE_WIN_LEAD };
+typedef struct { int32_t fn; int32_t column; int64_t offset; } qe_window_fn;  /* column: argument (ignored by the three ranks); offset: LAG/LEAD only */
+int32_t qe_result_window(qe_ctx *ctx, const qe_result *result,
+                         const int32_t *partition_cols, int32_t npart,
+                         const qe_sort_key *order, int32_t norder,
+                         const qe_window_fn *fns, int32_t nfn, qe_result **out);
+/* what the last qe_result_window of this context did: out[0] rows, out[1] partitions, out[2] scan tiles (2048 rows each),
+ * out[3] trips of the tile-aggregate scan (1024 tiles each) */
+int32_t qe_ctx_last_window_stats(const qe_ctx *ctx, int64_t out[4]);
+
 /* zero-copy: a batch whose columns ARE the result's (not owned; the result must outlive the batch).  Same columns, same
  * validity (NULL where the result has none), same dictionaries, nrows = the result's count (zero rows: a zero-row batch).
  * The batch goes into qe_filter_project / qe_filter_aggregate / qe_filter_groupby like any other: that is how a join is

@@ -64,6 +64,12 @@ internal object QeNative {
     // int build_out[m], m (0 for SEMI / ANTI), qe_result** -> status: rows in nested-loop order, probe side outside
     val qe_join_probe = handle("qe_join_probe", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS)
     val qe_ctx_last_join_stats = handle("qe_ctx_last_join_stats", JAVA_INT, ADDRESS, ADDRESS)         // ctx, long[4]
+    // ---- window functions over a result (ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW inside the partition) ----
+    // ctx, result, int partition_cols[npart], npart, qe_sort_key order[norder], norder, qe_window_fn fns[nfn] {int fn, int column,
+    // long offset}, nfn (1..16), qe_result** -> status: every input column sorted by (partition, order), then one column per function
+    // (fn: 0 ROW_NUMBER, 1 RANK, 2 DENSE_RANK, 3 SUM, 4 COUNT, 5 MIN, 6 MAX, 7 AVG, 8 LAG, 9 LEAD)
+    val qe_result_window = handle("qe_result_window", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS)
+    val qe_ctx_last_window_stats = handle("qe_ctx_last_window_stats", JAVA_INT, ADDRESS, ADDRESS)     // ctx, long[4]
     // ctx, result, qe_batch** -> status: a batch whose columns ARE the result's (zero copy): the input of the next plan
     val qe_batch_from_result = handle("qe_batch_from_result", JAVA_INT, ADDRESS, ADDRESS, ADDRESS)
 

@@ -4,6 +4,7 @@
 //   qe_groupby.cpp   the global aggregate and the GROUP BY routes with their entry points
 //   qe_result.cpp    results on the device and their way to the host
 //   qe_join.cpp      the hash equi-join of two device-resident sides, a result as the next plan's batch
+//   qe_window.cpp    window functions over a result: the sort, the boundary flags, the segmented scans
 #pragma once
 
 #include <memory>

@@ -430,6 +430,7 @@ struct qe_ctx {
     qe_csv_device_stats csv_stats{};   // what the last qe_csv_parse*_device call did
     int64_t sort_stats[4] = {0, 0, 0, 0};   // qe_ctx_last_sort_stats: path, rows sorted, radix passes, selection passes
     int64_t join_stats[4] = {0, 0, 0, 0};   // qe_ctx_last_join_stats: build rows in the table, probe rows, output rows, longest run walked
+    int64_t window_stats[4] = {0, 0, 0, 0}; // qe_ctx_last_window_stats: rows, partitions, scan tiles, trips of the tile-aggregate scan
 };
 
 struct qe_host_result {

@@ -145,6 +145,50 @@ void launch_join_gather(hipStream_t s, int width, const void *src, const uint32_
 // bit j of out = bit rows[j] of src (src null: 1), 0 for row 0xFFFFFFFF; whole words are written
 void launch_join_gather_bits(hipStream_t s, const uint64_t *src, const uint32_t *rows, int64_t n, uint64_t *out);
 
+// ---- window functions over a sorted result (qe_window.hip) ----
+constexpr int kWinTileRows = 2048;    // T: rows of one scan tile (4 waves x 8 words of 64 rows)
+constexpr int kWinTripTiles = 1024;   // tile aggregates one trip of the one-workgroup scan holds
+// Boundary flags of the sorted rows: bit j of pstart = row j starts a partition (row 0, or it differs from row j - 1 in the
+// sort image or the validity of one of the first npart keys), bit j of peer = it starts a partition or differs on a later
+// key.  perm[j] = source row that stands at j (null: j itself).  *npartitions += set bits of pstart.
+struct WinFlagArgs {
+    int nkeys, npart;
+    int type[8];
+    const void *data[8];
+    const unsigned long long *validity[8];
+    const int *ranks[8];                    // QE_STRING: compareTo rank per dictionary code (the sort's table)
+    int nranks[8];
+    const unsigned int *perm;
+    long long n;
+    unsigned long long *pstart, *peer;      // ceil(n / 64) words each, whole words are written
+    unsigned long long *npartitions;
+};
+void launch_win_flags(hipStream_t s, const WinFlagArgs &a);
+// One segmented inclusive scan over the n rows, restarted at every set bit of pstart, in three fixed-shape steps: per-tile
+// reduce, one workgroup over the tile aggregates (kWinTripTiles per trip), per-tile downsweep.
+enum { QE_WSCAN_SUM = 0, QE_WSCAN_MIN = 1, QE_WSCAN_MAX = 2, QE_WSCAN_INDEX = 3 };
+enum { QE_WOUT_SUM = 0, QE_WOUT_MINMAX = 1, QE_WOUT_AVG = 2, QE_WOUT_COUNT = 3, QE_WOUT_COUNT_I64 = 4, QE_WOUT_INDEX = 5 };
+struct WinScanArgs {
+    int op;                                 // QE_WSCAN_*
+    int out_mode;                           // QE_WOUT_*
+    int type;                               // QE_DOUBLE / QE_INT64 / QE_INT32 of data
+    const void *data;                       // null: only the count of valid rows is scanned
+    const unsigned long long *validity;     // null: every row valid.  QE_WSCAN_INDEX: the bitmap whose last set bit at or before each row is wanted
+    const unsigned long long *pstart;       // null: one segment
+    long long n, ntiles;
+    double *tile_v, *carry_v;               // ntiles each: the tile aggregates, and what the scan over them carries into each tile
+    unsigned int *tile_c, *tile_f, *carry_c;
+    void *out;                              // f64 (SUM, MINMAX, AVG, COUNT), i64 (COUNT_I64) or u32 (INDEX) per row
+    unsigned long long *out_valid;          // SUM, MINMAX, AVG: bit j = a valid value has been seen in the partition up to row j
+};
+void launch_win_scan(hipStream_t s, const WinScanArgs &a);
+// out[j] = (first ? first[j] : j) - start[j] + 1: ROW_NUMBER (first null) and RANK (first = index of the first peer)
+void launch_win_rank(hipStream_t s, const uint32_t *start, const uint32_t *first, int64_t n, int64_t *out);
+// LAG / LEAD: out[j] = src[j + delta] where that row exists and start[j + delta] == start[j], else zero with validity 0;
+// width 8 / 4, or 0 for a bitmap column; src_valid null = every source row valid
+void launch_win_shift(hipStream_t s, int width, const void *src, const uint64_t *src_valid, const uint32_t *start, int64_t n,
+                      int64_t delta, void *out, uint64_t *out_valid);
+
 // place nbits bits of src at bit offset dst_bit_offset of dst (bitmap words; concatenation of results / gather)
 void launch_bitmap_place(hipStream_t s, uint64_t *dst, int64_t dst_bit_offset, const uint64_t *src, int64_t nbits);
 

@@ -10,40 +10,17 @@
 #include <hip/hip_runtime.h>
 
 #include "qe_kernels.h"
+#include "qe_sort_image.h"
 
 namespace qe {
 
-typedef unsigned long long u64;
-typedef long long i64;
-typedef unsigned int u32;
-
 // ---- sort keys -----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool bit_at(const u64 *bm, i64 i) { return (bm[i >> 6] >> (i & 63)) & 1ull; }
 
 __global__ void __launch_bounds__(256) sort_key_kernel(const SortKeyArgs a) {
     const i64 stride = (i64)gridDim.x * blockDim.x;
     for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < a.n; j += stride) {
         const i64 i = a.perm ? (i64)a.perm[j] : j;   // a later key of a multi-key sort: the image of the row that stands at j now
-        u64 k = 0;   // NULL: before every value (compareValues)
-        if (!a.validity || bit_at(a.validity, i)) {
-            switch (a.type) {
-            case QE_DOUBLE: {   // Double.compareTo: IEEE order with -0.0 < 0.0, every NaN equal and greatest
-                const double d = ((const double *)a.data)[i];
-                i64 b = d != d ? 0x7ff8000000000000ll : __builtin_bit_cast(i64, d);
-                b ^= (b >> 63) & 0x7fffffffffffffffll;            // negative values: reverse their order
-                k = ((u64)b ^ 0x8000000000000000ull);             // signed -> unsigned order
-                break;
-            }
-            case QE_INT64: k = (u64)((const i64 *)a.data)[i] ^ 0x8000000000000000ull; break;
-            case QE_INT32: k = (u64)(i64)((const int *)a.data)[i] ^ 0x8000000000000000ull; break;
-            case QE_STRING: {   // rank of the code in the dictionary's String.compareTo order (table from the host)
-                const int c = ((const int *)a.data)[i];
-                k = (u64)((u32)c < (u32)a.nranks ? a.ranks[c] : 0);
-                break;
-            }
-            default: k = bit_at((const u64 *)a.data, i) ? 1ull : 0ull; break;   // BOOLEAN bitmap
-            }
-        }   // (NULL rows keep key 0 and are moved in front by one last pass on the validity bit: launch_radix_pass with shift 64)
+        const u64 k = sort_image(a.type, a.data, a.validity, a.ranks, a.nranks, i);   // 0 under a NULL, which the pass on the validity bit (shift 64) moves in front
         // descending: the complement reverses the unsigned order (NULL becomes the greatest image; the validity pass with
         // shift 65 puts it behind every value, also behind a value whose image is all ones)
         a.keys[j] = a.descending ? ~k : k;

@@ -177,6 +177,26 @@ class Context:
         N.check(self.handle, self._lib.qe_ctx_last_join_stats(self.handle, out))
         return [int(v) for v in out]
 
+    def window(self, result: "Result", partition_by: Sequence[int], order_by: Sequence, functions: Sequence) -> "Result":
+        """qe_result_window: every row of `result`, sorted stably by `partition_by` (columns, ascending) and then by `order_by`
+        = [(column, descending), ...], followed by one column per entry of `functions` = [(native.WIN_*, column, offset), ...]
+        (column: the argument, ignored by the ranks; offset: LAG / LEAD only; shorter tuples are padded with zeros).  The frame
+        is ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW inside the partition."""
+        order_by = list(order_by)
+        fns = [(tuple(f) + (0, 0))[:3] for f in functions]
+        keys = (N.SortKey * max(1, len(order_by)))(*[N.SortKey(int(c), 1 if d else 0) for c, d in order_by])
+        arr = (N.WindowFn * max(1, len(fns)))(*[N.WindowFn(int(f), int(c), int(o)) for f, c, o in fns])
+        h = C.c_void_p()
+        N.check(self.handle, self._lib.qe_result_window(self.handle, result.handle, _i32_array(partition_by), len(partition_by),
+                                                        keys, len(order_by), arr, len(fns), C.byref(h)))
+        return Result(self, h)
+
+    def last_window_stats(self) -> dict:
+        """qe_ctx_last_window_stats: rows, partitions, scan tiles and trips of the tile-aggregate scan of the last window()."""
+        out = (C.c_int64 * 4)()
+        N.check(self.handle, self._lib.qe_ctx_last_window_stats(self.handle, out))
+        return {"rows": int(out[0]), "partitions": int(out[1]), "tiles": int(out[2]), "trips": int(out[3])}
+
     def concat(self, parts: Sequence["Result"]) -> "Result":
         """qe_result_concat: results of this device, concatenated in the given order."""
         arr = (C.c_void_p * max(1, len(parts)))(*[p.handle for p in parts])

@@ -30,6 +30,8 @@ COMM_ID_BYTES = 128
 FORM_RING, FORM_TWO_PASS, FORM_DENSE, FORM_PER_NODE, FORM_NO_FILTER, FORM_LOCAL = range(6)
 FORM_GROUPBY_DENSE, FORM_GROUPBY_HASHED, FORM_GROUPBY_HASH_PARTITIONED = 8, 9, 10
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = range(4)
+WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_SUM, WIN_COUNT, WIN_MIN, WIN_MAX, WIN_AVG, WIN_LAG, WIN_LEAD = range(10)
+WIN_TILE_ROWS, WIN_TRIP_TILES = 2048, 1024   # the scan's tile and the tile aggregates one trip covers
 
 
 class QeError(RuntimeError):
@@ -72,6 +74,11 @@ class SortKey(C.Structure):
 class JoinInput(C.Structure):
     """qe_join_input: one side of a join, a result or a batch (exactly one is set)."""
     _fields_ = [("result", C.c_void_p), ("batch", C.c_void_p)]
+
+
+class WindowFn(C.Structure):
+    """qe_window_fn: one window function (column: its argument, ignored by the ranks; offset: LAG / LEAD only)."""
+    _fields_ = [("fn", C.c_int32), ("column", C.c_int32), ("offset", C.c_int64)]
 
 
 # every symbol include/qe_hip.h declares: (name, restype, argtypes)
@@ -144,6 +151,8 @@ SYMBOLS = [
     ("qe_join_probe", C.c_int32, [_P, _P, C.POINTER(JoinInput), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                   C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_P)]),
     ("qe_ctx_last_join_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
+    ("qe_result_window", C.c_int32, [_P, _P, C.POINTER(C.c_int32), C.c_int32, _P, C.c_int32, C.POINTER(WindowFn), C.c_int32, C.POINTER(_P)]),
+    ("qe_ctx_last_window_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_batch_from_result", C.c_int32, [_P, _P, C.POINTER(_P)]),
     ("qe_comm_unique_id", C.c_int32, [_P, _P]),
     ("qe_comm_init", C.c_int32, [_P, C.c_int32, C.c_int32, _P]),

@@ -267,6 +267,152 @@ class HashJoinOperator(Operator):
             self._result = None
 
 
+def _window_min(a: float, b: float, want_max: bool) -> float:
+    """MIN / MAX of two doubles as the aggregates decide them: NaN wins, -0.0 is below +0.0."""
+    if a != a:
+        return a
+    if b != b:
+        return b
+    if want_max:
+        return b if _compare_key(b) > _compare_key(a) else a
+    return b if _compare_key(b) < _compare_key(a) else a
+
+
+class WindowOperator(Operator):
+    """Window functions over a source: every source row, sorted stably by ``partition_by`` (column indices, ascending) and
+    then by ``order_by`` (``[(column, descending), ...]``, the comparator of ``OrderByOperator``), followed by one value
+    per entry of ``functions`` = ``[(fn, column, offset), ...]`` (``fn`` one of ``native.WIN_*``; ``column`` is ignored by the
+    three ranks, ``offset`` is read by LAG / LEAD only; shorter tuples are padded with zeros).
+
+    Adjacent rows share a partition when they compare equal on every partition column (``None`` is a key value, all NaNs
+    are one value, -0.0 and 0.0 are two); peers are rows of a partition that compare equal on every order key.  The frame
+    is always ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW.  ROW_NUMBER, RANK (the row number of the first peer) and
+    DENSE_RANK are ints; SUM / MIN / MAX / AVG skip ``None`` and are ``None`` until the partition has shown a value; COUNT
+    counts the values so far (an int, like the COUNT of the aggregation operators); LAG / LEAD give the value ``offset``
+    rows before / after in the partition, ``None`` beyond its edge.  The reference has no windows (Query.g4).
+
+    When the source is a GPU operator (``result()`` and ``ctx``) the rows never leave HBM (qe_result_window) and the
+    operator offers ``result()`` and ``ctx`` itself.  Any other source is drained and evaluated on the host: stable sorts
+    with ``_compare_key``, then one sequential loop per partition -- the executable statement of the semantics, and the
+    expectation of the device tests."""
+
+    def __init__(self, source: Operator, partition_by: Sequence[int], order_by: Sequence, functions: Sequence):
+        self.source = source
+        self.partition_by = [int(c) for c in partition_by]
+        self.order_by = [(int(c), bool(d)) for c, d in order_by]
+        self.functions = [tuple(int(v) for v in (tuple(f) + (0, 0))[:3]) for f in functions]
+        if len(self.partition_by) + len(self.order_by) > 8:
+            raise ValueError("WindowOperator: at most 8 partition and order columns")
+        if not 1 <= len(self.functions) <= 16:
+            raise ValueError("WindowOperator: 1 to 16 functions")
+        for fn, _, offset in self.functions:
+            if not N.WIN_ROW_NUMBER <= fn <= N.WIN_LEAD:
+                raise ValueError("WindowOperator: unknown window function")
+            if fn in (N.WIN_LAG, N.WIN_LEAD) and not 0 <= offset < 2 ** 31:
+                raise ValueError("WindowOperator: 0 <= offset < 2^31")
+        self._on_device = hasattr(source, "result") and hasattr(source, "ctx")
+        if self._on_device:
+            self.ctx = source.ctx
+        self._result: Optional[E.Result] = None
+        self._iter = None
+
+    def _device_rows(self):
+        cols = self._result.to_columns()
+        first = len(cols) - len(self.functions)
+        for i in range(len(cols[0]) if cols else 0):
+            row = [c.value(i) for c in cols]
+            for k, (fn, _, _) in enumerate(self.functions):
+                if fn == N.WIN_COUNT:
+                    row[first + k] = int(row[first + k])
+            yield row
+
+    def _rows_host(self) -> List[List[Any]]:
+        data = mapTo(self.source, [], lambda row: list(row))
+        for column, descending in reversed([(c, False) for c in self.partition_by] + self.order_by):
+            data.sort(key=lambda row: _compare_key(row[column]), reverse=descending)
+        for fn, column, _ in self.functions:
+            if fn in (N.WIN_SUM, N.WIN_MIN, N.WIN_MAX, N.WIN_AVG):
+                for row in data:
+                    if isinstance(row[column], (bool, str)):
+                        raise ValueError("WindowOperator: SUM / MIN / MAX / AVG need a numeric column")
+
+        def same(a, b, columns):
+            return all(_compare_key(a[c]) == _compare_key(b[c]) for c in columns)
+        out = []
+        begin = 0
+        while begin < len(data):
+            end = begin + 1
+            while end < len(data) and same(data[end], data[begin], self.partition_by):
+                end += 1
+            part = data[begin:end]
+            values = [[] for _ in self.functions]
+            for k, (fn, column, offset) in enumerate(self.functions):
+                rank = dense = 0
+                total, count, extreme = 0.0, 0, None      # Accumulators.kt:40: a sum starts from 0.0
+                for i, row in enumerate(part):
+                    if i == 0 or not same(row, part[i - 1], [c for c, _ in self.order_by]):
+                        rank, dense = i + 1, dense + 1
+                    v = row[column] if fn >= N.WIN_SUM else None
+                    if fn == N.WIN_ROW_NUMBER:
+                        values[k].append(i + 1)
+                    elif fn == N.WIN_RANK:
+                        values[k].append(rank)
+                    elif fn == N.WIN_DENSE_RANK:
+                        values[k].append(dense)
+                    elif fn == N.WIN_LAG:
+                        values[k].append(part[i - offset][column] if i - offset >= 0 else None)
+                    elif fn == N.WIN_LEAD:
+                        values[k].append(part[i + offset][column] if i + offset < len(part) else None)
+                    else:
+                        if v is not None:
+                            count += 1
+                            if fn in (N.WIN_SUM, N.WIN_AVG):
+                                total += float(v)
+                            elif fn in (N.WIN_MIN, N.WIN_MAX):
+                                extreme = float(v) if extreme is None else _window_min(extreme, float(v), fn == N.WIN_MAX)
+                        if fn == N.WIN_COUNT:
+                            values[k].append(count)
+                        elif count == 0:
+                            values[k].append(None)
+                        elif fn == N.WIN_SUM:
+                            values[k].append(total)
+                        elif fn == N.WIN_AVG:
+                            values[k].append(total / count)
+                        else:
+                            values[k].append(extreme)
+            out.extend(row + [values[k][i] for k in range(len(self.functions))] for i, row in enumerate(part))
+            begin = end
+        return out
+
+    def open(self) -> None:
+        if self._on_device:
+            self.source.open()
+            try:
+                self._result = self.ctx.window(self.source.result(), self.partition_by, self.order_by, self.functions)
+            finally:
+                self.source.close()
+            self._iter = self._device_rows()
+        else:
+            self._iter = iter(self._rows_host())
+
+    def result(self) -> E.Result:
+        """The windowed columns in HBM (valid until close()); only when the source is a GPU operator."""
+        if self._result is None:
+            raise RuntimeError("Operator not initialized")
+        return self._result
+
+    def next(self) -> Optional[List[Any]]:
+        if self._iter is None:
+            raise RuntimeError("Operator not opened")
+        return next(self._iter, None)
+
+    def close(self) -> None:
+        self._iter = None
+        if self._result is not None:
+            self._result.free()
+            self._result = None
+
+
 class ColumnarScanOperator(Operator):
     """Scan leaf over a ColumnarTable (replaces MemorySourceOperator.kt:5-36).
 
