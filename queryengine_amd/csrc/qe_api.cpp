@@ -878,14 +878,14 @@ void alloc_outputs(qe_ctx *ctx, const Plan &plan, qe_result *res, int64_t cap, F
     for (size_t i = 0; i < res->cols.size(); i++) {
         OutColumn &oc = res->cols[i];
         if (oc.type == QE_BOOLEAN) {
-            oc.bytes_data = ctx->pool.alloc((size_t)std::max<int64_t>(cap, 1));
+            oc.bytes_data = ctx->pool.alloc((size_t)cap);
             p.out[i] = oc.bytes_data;
         } else {
-            oc.data = ctx->pool.alloc(std::max<size_t>(type_width(oc.type) * (size_t)cap, 16));
+            oc.data = ctx->pool.alloc(type_width(oc.type) * (size_t)cap);
             p.out[i] = oc.data;
         }
         if (oc.nullable) {
-            oc.bytes_valid = (uint8_t *)ctx->pool.alloc((size_t)std::max<int64_t>(cap, 1));
+            oc.bytes_valid = (uint8_t *)ctx->pool.alloc((size_t)cap);
             p.outvalid[i] = oc.bytes_valid;
         }
     }
@@ -896,12 +896,12 @@ void pack_byte_columns(qe_ctx *ctx, qe_result *res) {
     bool packed = false;
     for (OutColumn &oc : res->cols) {
         if (oc.type == QE_BOOLEAN) {
-            oc.data = ctx->pool.alloc(std::max<size_t>(bitmap_bytes(res->count), 16));
+            oc.data = ctx->pool.alloc(bitmap_bytes(res->count));
             launch_pack_bytes(ctx->stream, (const uint8_t *)oc.bytes_data, res->count, (uint64_t *)oc.data);
             packed = true;
         }
         if (oc.nullable) {
-            oc.validity = (uint64_t *)ctx->pool.alloc(std::max<size_t>(bitmap_bytes(res->count), 16));
+            oc.validity = (uint64_t *)ctx->pool.alloc(bitmap_bytes(res->count));
             launch_pack_bytes(ctx->stream, oc.bytes_valid, res->count, oc.validity);
             packed = true;
         }
@@ -938,8 +938,7 @@ qe_result *run_fused(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filter, 
     const GeoPick pick = pick_geometry_candidate(ctx, batch, ordered, obase);
     const Plan &plan = *pick.plan;
 
-    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(),
-                                                                      [ctx](qe_result *r) { free_result(ctx, r); });
+    ResultPtr res = new_result(ctx, 0);   // (the count is known after the scan)
     const int64_t cap = ctx->opts.result_capacity_rows > 0 ? std::min<int64_t>(ctx->opts.result_capacity_rows, n) : n;
     res->capacity = cap;
     for (const OutSpec &os : plan.cg.outs) {

@@ -15,13 +15,10 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <functional>
 #include <numeric>
 
-#include "qe_internal.h"
+#include "qe_exec.h"
 #include "qe_kernels.h"
-#include "qe_pernode_kernels.h"
-#include "qe_sort_driver.h"
 
 namespace qe {
 
@@ -83,9 +80,6 @@ static void nccl_check(int r, const char *what) {
     fail(QE_ERR_COMM, std::string(what) + " failed: " + (msg ? msg : "?") + " (" + std::to_string(r) + ")");
 }
 #define QE_NCCL(x) ::qe::nccl_check((x), #x)
-
-static size_t width_of(int t) { return (t == QE_DOUBLE || t == QE_INT64) ? 8 : (t == QE_INT32 || t == QE_STRING) ? 4 : 0; }
-static size_t words_of(int64_t n) { return (size_t)((n + 63) / 64); }
 
 // Fingerprint of a dictionary: STRING columns travel as raw codes, so every rank must hold the SAME dictionary (same
 // entries in the same order) or the root would decode a peer's codes to the wrong strings.
@@ -152,51 +146,22 @@ struct RcclGroup {
 };
 
 // The output result of a concatenation / gather: per column a values buffer for `total` rows and, if any part carries a
-// validity bitmap, a validity bitmap (parts without one contribute ones).
-static qe_result *make_output(qe_ctx *ctx, const qe_result *like, int64_t total, uint32_t any_validity) {
-    std::unique_ptr<qe_result> out(new qe_result());
-    out->count = total;
-    out->capacity = total;
-    try {
-        for (size_t c = 0; c < like->cols.size(); c++) {
-            const OutColumn &src = like->cols[c];
-            OutColumn oc;
-            oc.type = src.type;
-            oc.dict = src.dict;
-            oc.dict_handle.d = src.dict;
-            oc.nullable = (any_validity >> c) & 1u;
-            out->cols.push_back(oc);
-            OutColumn &dst = out->cols.back();
-            const size_t nb = src.type == QE_BOOLEAN ? words_of(total) * 8 : width_of(src.type) * (size_t)total;
-            dst.data = ctx->pool.alloc(std::max<size_t>(nb, 16));
-            if (src.type == QE_BOOLEAN && nb) QE_HIP(hipMemsetAsync(dst.data, 0, nb, ctx->stream));
-            if (dst.nullable) {
-                dst.validity = (uint64_t *)ctx->pool.alloc(std::max<size_t>(words_of(total) * 8, 16));
-                if (total > 0) QE_HIP(hipMemsetAsync(dst.validity, 0, words_of(total) * 8, ctx->stream));
-            }
-        }
-    } catch (...) {
-        for (auto &c : out->cols) {
-            ctx->pool.release(c.data);
-            ctx->pool.release(c.validity);
-        }
-        throw;
+// validity bitmap, a validity bitmap (parts without one contribute ones).  Bitmaps are zeroed: bitmap_place ORs segments in.
+static ResultPtr make_output(qe_ctx *ctx, const qe_result *like, int64_t total, uint32_t any_validity) {
+    ResultPtr out = new_result(ctx, total);
+    for (size_t c = 0; c < like->cols.size(); c++) {
+        const OutColumn &src = like->cols[c];
+        OutColumn &dst = add_column(ctx, out.get(), src.type, (any_validity >> c) & 1u, src.dict, total);
+        if (total == 0) continue;
+        if (src.type == QE_BOOLEAN) QE_HIP(hipMemsetAsync(dst.data, 0, bitmap_bytes(total), ctx->stream));
+        if (dst.nullable) QE_HIP(hipMemsetAsync(dst.validity, 0, bitmap_bytes(total), ctx->stream));
     }
-    return out.release();
-}
-
-static void free_output(qe_ctx *ctx, qe_result *r) {
-    if (!r) return;
-    for (auto &c : r->cols) {
-        ctx->pool.release(c.data);
-        ctx->pool.release(c.validity);
-    }
-    delete r;
+    return out;
 }
 
 static uint64_t *ones_bitmap(qe_ctx *ctx, PoolScratch &sc, int64_t n) {
-    uint64_t *p = (uint64_t *)sc.alloc(words_of(n) * 8);
-    QE_HIP(hipMemsetAsync(p, 0xff, words_of(n) * 8, ctx->stream));
+    uint64_t *p = (uint64_t *)sc.alloc(bitmap_bytes(n));
+    QE_HIP(hipMemsetAsync(p, 0xff, bitmap_bytes(n), ctx->stream));
     return p;
 }
 
@@ -204,135 +169,17 @@ static uint64_t *ones_bitmap(qe_ctx *ctx, PoolScratch &sc, int64_t n) {
 
 using namespace qe;
 
-template <typename F>
-static int32_t guarded_comm(qe_ctx *ctx, F &&f) {
-    try {
-        f();
-        return QE_OK;
-    } catch (const Error &e) {
-        if (ctx) ctx->last_error = e.msg;
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        if (ctx) ctx->last_error = "host out of memory";
-        return QE_ERR_OOM;
-    } catch (const std::exception &e) {
-        if (ctx) ctx->last_error = e.what();
-        return QE_ERR_INTERNAL;
-    }
-}
-
-static void need_dev(const qe_ctx *ctx) {
-    if (ctx->device < 0) fail(QE_ERR_HIP, "planning-only context (QE_DEVICE_NONE): this call needs a HIP device");
-    QE_HIP(hipSetDevice(ctx->device));
-}
-
-// ORDER BY on the device: OrderByOperator.open (operator/OrderByOperator.kt:9-15) sorts the materialised rows stably
-// with compareValues -- null first, Double.compareTo (-0.0 < 0.0, NaN greatest), String.compareTo (UTF-16 code units),
-// false < true.  Key images + stable LSD radix sort of (key, row id) + gather of every column (qe_sort.hip).
-//
-// Several keys: the sort is stable, so it runs once per key from the LAST key to the first; the image of every key after
-// the first one sorted is taken through the permutation reached so far, so the scratch stays two (u64, u32) buffers.  A
-// descending key sorts the complement of its image and puts NULL last; ties keep their input order in both directions.
-//
-// LIMIT k (0 < k <= n / kTopkMaxShareDen; a larger k would make at least k rows candidates and goes straight to the full
-// sort, truncated): radix select of the k-th smallest image of the FIRST key (NULL is the smallest image ascending and
-// the greatest descending, so the NULL class is part of the order), the rows up to that threshold -- every tie of it
-// included -- are compacted in row order, and only these c candidates go through the multi-key sort.  The first k sorted
-// row ids are gathered.  When c exceeds n / kTopkMaxShareDen (a boolean or few-valued first key) the full sort runs instead.
-namespace {
-
-constexpr int64_t kTopkMaxShareDen = 2;       // candidates > n / 2: the full sort is taken (selection + the sort of c rows would cost as much)
-constexpr int64_t kTopkStopFloor = 16384;     // the selection stops once this few rows are left (sorting them costs no more than one pass)
-
-void order_by_impl(qe_ctx *ctx, const qe_result *src, const qe_sort_key *keys, int32_t nkeys, int64_t limit, const char *who, qe_result **out) {
-    need_dev(ctx);
-    const int64_t n = src->count;
-    if (n >= (1ll << 32)) fail(QE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 rows");
-    for (int32_t k = 0; k < nkeys; k++)
-        if (keys[k].column < 0 || keys[k].column >= (int32_t)src->cols.size()) fail(QE_ERR_INVALID_ARG, std::string(who) + ": key column out of range");
-    const int64_t nout = limit >= 0 && limit < n ? limit : n;
-    uint32_t any_validity = 0;
-    for (size_t c = 0; c < src->cols.size(); c++)
-        if (src->cols[c].validity) any_validity |= 1u << c;
-    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(make_output(ctx, src, nout, any_validity),
-                                                                      [ctx](qe_result *r) { free_output(ctx, r); });
-    int64_t stats[4] = {0, 0, 0, 0};
-    if (nout > 0) {
-        PoolScratch sc(ctx);
-        SortDriver drv{ctx, sc, src, keys, nkeys};
-        drv.prepare();
-        unsigned long long *kbuf[2] = {nullptr, nullptr};
-        uint32_t *rbuf[2] = {nullptr, nullptr};
-        int64_t m = n;          // rows that go into the sort
-        bool identity = true;
-        if (nout < n && nout <= n / kTopkMaxShareDen) {
-            // ---- top-k: select on the first key's images, candidates in row order ----
-            unsigned long long *img = (unsigned long long *)sc.alloc((size_t)n * 8);
-            drv.images(0, n, nullptr, img, nullptr);
-            const unsigned long long var = drv.varying(img, n);
-            SelectState *st = (SelectState *)sc.alloc(sizeof(SelectState));
-            SelectState init{};
-            init.remaining = (unsigned long long)nout;
-            QE_HIP(hipMemcpyAsync(st, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
-            const unsigned long long stop_cap = (unsigned long long)std::max<int64_t>(nout + nout / 4, std::min<int64_t>(kTopkStopFloor, n / 16));
-            for (int shift = 56; shift >= 0; shift -= 8) {
-                if (((var >> shift) & 255ull) == 0) continue;   // the same digit in every key
-                launch_select_pass(ctx->stream, img, n, shift, st, stop_cap);
-            }
-            const int64_t nblocks = select_compact_blocks(n);
-            uint32_t *counts = (uint32_t *)sc.alloc((size_t)nblocks * 4), *offsets = (uint32_t *)sc.alloc((size_t)nblocks * 4);
-            uint32_t *sums = (uint32_t *)sc.alloc((size_t)((nblocks + 1023) / 1024) * 4);
-            unsigned long long *d_total = (unsigned long long *)sc.alloc(16);
-            launch_select_count(ctx->stream, img, n, st, counts);
-            pn::exclusive_scan_u32(ctx->stream, counts, offsets, sums, nblocks, d_total);
-            unsigned long long c = 0;
-            unsigned int passes = 0;
-            QE_HIP(hipMemcpyAsync(&c, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));   // the one read-back of the selection
-            QE_HIP(hipMemcpyAsync(&passes, &st->passes, 4, hipMemcpyDeviceToHost, ctx->stream));
-            QE_HIP(hipStreamSynchronize(ctx->stream));
-            if ((int64_t)c < nout || (int64_t)c > n) fail(QE_ERR_INTERNAL, std::string(who) + ": top-k selection kept " + std::to_string(c) + " of " +
-                                                                                std::to_string(n) + " rows for k = " + std::to_string(nout));
-            stats[3] = passes;
-            if ((int64_t)c <= n / kTopkMaxShareDen) {
-                m = (int64_t)c;
-                identity = false;
-                stats[0] = 1;
-                rbuf[0] = (uint32_t *)sc.alloc((size_t)m * 4);
-                launch_select_compact(ctx->stream, img, n, st, counts, offsets, rbuf[0], m);
-                kbuf[0] = (unsigned long long *)sc.alloc((size_t)m * 8);
-            } else {
-                kbuf[0] = img;   // too many candidates: the full sort, truncated
-            }
-        }
-        if (!kbuf[0]) kbuf[0] = (unsigned long long *)sc.alloc((size_t)m * 8);
-        kbuf[1] = (unsigned long long *)sc.alloc((size_t)m * 8);
-        if (!rbuf[0]) rbuf[0] = (uint32_t *)sc.alloc((size_t)m * 4);
-        rbuf[1] = (uint32_t *)sc.alloc((size_t)m * 4);
-        uint32_t *hist = (uint32_t *)sc.alloc((size_t)((m + 1023) / 1024) * 16 * 4);
-        const int cur = drv.sort(m, identity, kbuf, rbuf, hist);
-        stats[1] = m;
-        stats[2] = drv.radix_passes;
-        gather_all_columns(ctx, src, rbuf[cur], nout, res.get());
-        QE_HIP(hipGetLastError());
-        QE_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    for (int i = 0; i < 4; i++) ctx->sort_stats[i] = stats[i];
-    *out = res.release();
-}
-
-}  // namespace
-
 extern "C" {
 
 int32_t qe_comm_unique_id(qe_ctx *ctx, qe_comm_id *out) {
     if (!ctx || !out) return QE_ERR_INVALID_ARG;
-    return guarded_comm(ctx, [&] { QE_NCCL(rccl().GetUniqueId(out)); });
+    return guarded(ctx, [&] { QE_NCCL(rccl().GetUniqueId(out)); });
 }
 
 int32_t qe_comm_init(qe_ctx *ctx, int32_t nranks, int32_t rank, const qe_comm_id *id) {
     if (!ctx || !id || nranks < 1 || rank < 0 || rank >= nranks) return QE_ERR_INVALID_ARG;
-    return guarded_comm(ctx, [&] {
-        need_dev(ctx);
+    return guarded(ctx, [&] {
+        need_device(ctx);
         if (ctx->comm) fail(QE_ERR_INVALID_ARG, "qe_comm_init: this context already has a communicator");
         void *comm = nullptr;
         QE_NCCL(rccl().CommInitRank(&comm, nranks, *id, rank));
@@ -359,8 +206,8 @@ void qe_comm_destroy(qe_ctx *ctx) {
 // partials, counts).  SURVEY 8f: "Cross-GPU: reduce of the per-GPU partials" -- folded by the host in rank order.
 int32_t qe_comm_allgather_host(qe_ctx *ctx, const void *send, size_t nbytes, void *recv) {
     if (!ctx || !send || !recv || nbytes == 0) return QE_ERR_INVALID_ARG;
-    return guarded_comm(ctx, [&] {
-        need_dev(ctx);
+    return guarded(ctx, [&] {
+        need_device(ctx);
         if (!ctx->comm) fail(QE_ERR_COMM, "qe_comm_allgather_host: no communicator (qe_comm_init)");
         PoolScratch sc(ctx);
         const size_t n = (size_t)ctx->comm_nranks;
@@ -376,8 +223,8 @@ int32_t qe_comm_allgather_host(qe_ctx *ctx, const void *send, size_t nbytes, voi
 int32_t qe_result_concat(qe_ctx *ctx, const qe_result *const *parts, int32_t nparts, qe_result **out) {
     if (!ctx || !out || nparts < 1 || !parts) return QE_ERR_INVALID_ARG;
     *out = nullptr;
-    return guarded_comm(ctx, [&] {
-        need_dev(ctx);
+    return guarded(ctx, [&] {
+        need_device(ctx);
         int64_t total = 0;
         uint32_t any_validity = 0;
         for (int32_t i = 0; i < nparts; i++) {
@@ -393,8 +240,7 @@ int32_t qe_result_concat(qe_ctx *ctx, const qe_result *const *parts, int32_t npa
             any_validity |= h.validity_mask;
         }
         PoolScratch sc(ctx);
-        std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(make_output(ctx, parts[0], total, any_validity),
-                                                                          [ctx](qe_result *r) { free_output(ctx, r); });
+        ResultPtr res = make_output(ctx, parts[0], total, any_validity);
         int64_t off = 0;
         for (int32_t i = 0; i < nparts; i++) {
             const int64_t n = parts[i]->count;
@@ -405,7 +251,7 @@ int32_t qe_result_concat(qe_ctx *ctx, const qe_result *const *parts, int32_t npa
                 if (src.type == QE_BOOLEAN)
                     launch_bitmap_place(ctx->stream, (uint64_t *)dst.data, off, (const uint64_t *)src.data, n);
                 else
-                    QE_HIP(hipMemcpyAsync((char *)dst.data + width_of(src.type) * (size_t)off, src.data, width_of(src.type) * (size_t)n,
+                    QE_HIP(hipMemcpyAsync((char *)dst.data + type_width(src.type) * (size_t)off, src.data, type_width(src.type) * (size_t)n,
                                           hipMemcpyDeviceToDevice, ctx->stream));
                 if (dst.nullable)
                     launch_bitmap_place(ctx->stream, dst.validity, off, src.validity ? src.validity : ones_bitmap(ctx, sc, n), n);
@@ -416,25 +262,6 @@ int32_t qe_result_concat(qe_ctx *ctx, const qe_result *const *parts, int32_t npa
         QE_HIP(hipStreamSynchronize(ctx->stream));
         *out = res.release();
     });
-}
-
-int32_t qe_result_order_by(qe_ctx *ctx, const qe_result *src, int32_t column, qe_result **out) {
-    if (!ctx || !src || !out || column < 0 || column >= (int32_t)src->cols.size()) return QE_ERR_INVALID_ARG;
-    *out = nullptr;
-    const qe_sort_key key{column, 0};
-    return guarded_comm(ctx, [&] { order_by_impl(ctx, src, &key, 1, -1, "qe_result_order_by", out); });
-}
-
-int32_t qe_result_order_by_keys(qe_ctx *ctx, const qe_result *src, const qe_sort_key *keys, int32_t nkeys, int64_t limit, qe_result **out) {
-    if (out) *out = nullptr;
-    if (!ctx || !src || !out || !keys || nkeys < 1 || nkeys > 8) return QE_ERR_INVALID_ARG;
-    return guarded_comm(ctx, [&] { order_by_impl(ctx, src, keys, nkeys, limit, "qe_result_order_by_keys", out); });
-}
-
-int32_t qe_ctx_last_sort_stats(const qe_ctx *ctx, int64_t out[4]) {
-    if (!ctx || !out) return QE_ERR_INVALID_ARG;
-    for (int i = 0; i < 4; i++) out[i] = ctx->sort_stats[i];
-    return QE_OK;
 }
 
 // Materialise a sharded result on rank `root`: *out is the concatenation in rank order there, NULL elsewhere.
@@ -449,8 +276,8 @@ int32_t qe_ctx_last_sort_stats(const qe_ctx *ctx, int64_t out[4]) {
 int32_t qe_gather(qe_ctx *ctx, const qe_result *local, int32_t root, qe_result **out) {
     if (!ctx || !local || !out) return QE_ERR_INVALID_ARG;
     *out = nullptr;
-    return guarded_comm(ctx, [&] {
-        need_dev(ctx);
+    return guarded(ctx, [&] {
+        need_device(ctx);
         if (!ctx->comm) fail(QE_ERR_COMM, "qe_gather: no communicator (qe_comm_init)");
         const int nranks = ctx->comm_nranks, rank = ctx->comm_rank;
         if (root < 0 || root >= nranks) fail(QE_ERR_INVALID_ARG, "qe_gather: root out of range");
@@ -493,7 +320,7 @@ int32_t qe_gather(qe_ctx *ctx, const qe_result *local, int32_t root, qe_result *
         const int64_t n_me = mine.count;
 
         // (2) local allocations, then one status word per rank
-        std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(nullptr, [ctx](qe_result *r) { free_output(ctx, r); });
+        ResultPtr res = own_result(ctx, nullptr);
         std::vector<const uint64_t *> vsend(ncols, nullptr);   // what this rank contributes as validity words per column
         struct Staged { uint64_t *words; int64_t off, n; uint64_t *dst; };
         std::vector<Staged> staged;                            // root: received bitmap words waiting for their placement
@@ -509,14 +336,14 @@ int32_t qe_gather(qe_ctx *ctx, const qe_result *local, int32_t root, qe_result *
                 }
             }
             if (rank == root) {
-                res.reset(make_output(ctx, local, total, any_validity));
+                res = make_output(ctx, local, total, any_validity);
                 for (int r = 0; r < nranks; r++) {
                     const int64_t n = hdr[r].count;
                     if (n == 0 || r == root) continue;
                     for (size_t c = 0; c < ncols; c++) {
                         OutColumn &dst = res->cols[c];
-                        if (dst.type == QE_BOOLEAN) staged.push_back({(uint64_t *)sc.alloc(words_of(n) * 8), offset[r], n, (uint64_t *)dst.data});
-                        if (dst.nullable) staged.push_back({(uint64_t *)sc.alloc(words_of(n) * 8), offset[r], n, dst.validity});
+                        if (dst.type == QE_BOOLEAN) staged.push_back({(uint64_t *)sc.alloc(bitmap_bytes(n)), offset[r], n, (uint64_t *)dst.data});
+                        if (dst.nullable) staged.push_back({(uint64_t *)sc.alloc(bitmap_bytes(n)), offset[r], n, dst.validity});
                     }
                 }
             }
@@ -548,9 +375,9 @@ int32_t qe_gather(qe_ctx *ctx, const qe_result *local, int32_t root, qe_result *
                 RcclGroup group(nc);
                 for (size_t c = 0; c < ncols; c++) {
                     const OutColumn &src = local->cols[c];
-                    const size_t nb = src.type == QE_BOOLEAN ? words_of(n_me) * 8 : width_of(src.type) * (size_t)n_me;
+                    const size_t nb = column_bytes(src.type, n_me);
                     QE_NCCL(nc.Send(src.data, nb, kNcclUint8, root, ctx->comm, ctx->stream));
-                    if (vsend[c]) QE_NCCL(nc.Send(vsend[c], words_of(n_me) * 8, kNcclUint8, root, ctx->comm, ctx->stream));
+                    if (vsend[c]) QE_NCCL(nc.Send(vsend[c], bitmap_bytes(n_me), kNcclUint8, root, ctx->comm, ctx->stream));
                 }
                 group.end();
             }
@@ -566,11 +393,11 @@ int32_t qe_gather(qe_ctx *ctx, const qe_result *local, int32_t root, qe_result *
                 for (size_t c = 0; c < ncols; c++) {
                     OutColumn &dst = res->cols[c];
                     if (dst.type == QE_BOOLEAN)
-                        QE_NCCL(nc.Recv(staged[si++].words, words_of(n) * 8, kNcclUint8, r, ctx->comm, ctx->stream));
+                        QE_NCCL(nc.Recv(staged[si++].words, bitmap_bytes(n), kNcclUint8, r, ctx->comm, ctx->stream));
                     else
-                        QE_NCCL(nc.Recv((char *)dst.data + width_of(dst.type) * (size_t)offset[r], width_of(dst.type) * (size_t)n, kNcclUint8, r,
+                        QE_NCCL(nc.Recv((char *)dst.data + type_width(dst.type) * (size_t)offset[r], type_width(dst.type) * (size_t)n, kNcclUint8, r,
                                         ctx->comm, ctx->stream));
-                    if (dst.nullable) QE_NCCL(nc.Recv(staged[si++].words, words_of(n) * 8, kNcclUint8, r, ctx->comm, ctx->stream));
+                    if (dst.nullable) QE_NCCL(nc.Recv(staged[si++].words, bitmap_bytes(n), kNcclUint8, r, ctx->comm, ctx->stream));
                 }
             }
             group.end();
@@ -583,8 +410,8 @@ int32_t qe_gather(qe_ctx *ctx, const qe_result *local, int32_t root, qe_result *
                 if (src.type == QE_BOOLEAN)
                     launch_bitmap_place(ctx->stream, (uint64_t *)dst.data, offset[root], (const uint64_t *)src.data, n_me);
                 else
-                    QE_HIP(hipMemcpyAsync((char *)dst.data + width_of(src.type) * (size_t)offset[root], src.data,
-                                          width_of(src.type) * (size_t)n_me, hipMemcpyDeviceToDevice, ctx->stream));
+                    QE_HIP(hipMemcpyAsync((char *)dst.data + type_width(src.type) * (size_t)offset[root], src.data,
+                                          type_width(src.type) * (size_t)n_me, hipMemcpyDeviceToDevice, ctx->stream));
                 if (dst.nullable) launch_bitmap_place(ctx->stream, dst.validity, offset[root], vsend[c], n_me);
             }
         }
@@ -610,8 +437,8 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
                                  int32_t nproj, int32_t root, int32_t nslices, qe_result **out) {
     if (!ctx || !batch || !out || nproj < 0 || (nproj > 0 && !projections)) return QE_ERR_INVALID_ARG;
     *out = nullptr;
-    return guarded_comm(ctx, [&] {
-        need_dev(ctx);
+    return guarded(ctx, [&] {
+        need_device(ctx);
         if (!ctx->comm) fail(QE_ERR_COMM, "qe_filter_project_gather: no communicator (qe_comm_init)");
         const int nranks = ctx->comm_nranks, rank = ctx->comm_rank;
         if (root < 0 || root >= nranks) fail(QE_ERR_INVALID_ARG, "qe_filter_project_gather: root out of range");
@@ -625,8 +452,7 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
         std::vector<int64_t> counts = qe_int_count_slices(ctx, batch, filter, projections, nproj, &slice_rows, K);
         const int ns = (int)counts.size();     // <= K slices really exist (short shards have fewer)
         // (1) one all-gather: the usual header (shape of this rank's result: taken from a zero-row execution of the plan) + counts
-        std::unique_ptr<qe_result, std::function<void(qe_result *)>> probe(qe_int_run_fused_slice(ctx, batch, 0, 0, filter, projections, nproj),
-                                                                            [ctx](qe_result *r) { qe_result_free(ctx, r); });
+        const ResultPtr probe = own_result(ctx, qe_int_run_fused_slice(ctx, batch, 0, 0, filter, projections, nproj));
         struct SliceHeader {
             GatherHeader h;
             int64_t nslices;
@@ -671,7 +497,7 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
         }
         const size_t ncols = probe->cols.size();
         // (2) allocations, then one status word per rank (as qe_gather)
-        std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(nullptr, [ctx](qe_result *r) { free_output(ctx, r); });
+        ResultPtr res = own_result(ctx, nullptr);
         struct Staged { uint64_t *words; int64_t off, n; uint64_t *dst; };
         std::vector<std::vector<Staged>> staged((size_t)max_slices);   // root: per slice, in the order the receives are posted
         int32_t my_status = QE_OK;
@@ -679,12 +505,12 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
         const uint64_t *ones = nullptr;   // validity words of a column that is nullable on another rank only
         try {
             if ((any_validity & ~mine.h.validity_mask) != 0 && n_me > 0) {
-                uint64_t *w = (uint64_t *)sc.alloc(words_of(slice_rows) * 8);
-                QE_HIP(hipMemsetAsync(w, 0xff, words_of(slice_rows) * 8, ctx->stream));
+                uint64_t *w = (uint64_t *)sc.alloc(bitmap_bytes(slice_rows));
+                QE_HIP(hipMemsetAsync(w, 0xff, bitmap_bytes(slice_rows), ctx->stream));
                 ones = w;
             }
             if (rank == root) {
-                res.reset(make_output(ctx, probe.get(), total, any_validity));
+                res = make_output(ctx, probe.get(), total, any_validity);
                 for (int k = 0; k < max_slices; k++) {
                     for (int r = 0; r < nranks; r++) {
                         if (r == root || k >= hdr[r].nslices || hdr[r].count[k] == 0) continue;
@@ -693,8 +519,8 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
                         const int64_t n = hdr[r].count[k];
                         for (size_t c = 0; c < ncols; c++) {
                             OutColumn &dst = res->cols[c];
-                            if (dst.type == QE_BOOLEAN) staged[(size_t)k].push_back({(uint64_t *)sc.alloc(words_of(n) * 8), off, n, (uint64_t *)dst.data});
-                            if (dst.nullable) staged[(size_t)k].push_back({(uint64_t *)sc.alloc(words_of(n) * 8), off, n, dst.validity});
+                            if (dst.type == QE_BOOLEAN) staged[(size_t)k].push_back({(uint64_t *)sc.alloc(bitmap_bytes(n)), off, n, (uint64_t *)dst.data});
+                            if (dst.nullable) staged[(size_t)k].push_back({(uint64_t *)sc.alloc(bitmap_bytes(n)), off, n, dst.validity});
                         }
                     }
                 }
@@ -720,7 +546,7 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
                     fail(status[r], "qe_filter_project_gather: rank " + std::to_string(r) + " could not allocate its buffers; the exchange was not started");
         }
         // (3) slices: scan on the compute stream, transfers on the copy stream
-        std::vector<std::unique_ptr<qe_result, std::function<void(qe_result *)>>> parts;   // alive until their transfers have completed
+        std::vector<ResultPtr> parts;   // alive until their transfers have completed
         struct Drain {   // whatever happens, nothing in flight may outlive the buffers it reads or writes
             qe_ctx *c;
             ~Drain() { (void)hipStreamSynchronize(c->copy_stream); }
@@ -732,7 +558,7 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
             if (k < ns) {
                 const int64_t b = (int64_t)k * slice_rows, e = std::min<int64_t>(batch->nrows, b + slice_rows);
                 part = qe_int_run_fused_slice(ctx, batch, b, e - b, filter, projections, nproj);   // returns when the slice is complete
-                parts.emplace_back(part, [ctx](qe_result *r) { qe_result_free(ctx, r); });
+                parts.push_back(own_result(ctx, part));
                 n_k = part->count;
                 if (n_k != counts[(size_t)k])
                     fail(QE_ERR_INTERNAL, "qe_filter_project_gather: slice " + std::to_string(k) + " kept " + std::to_string(n_k) + " rows, the count pass said " +
@@ -743,10 +569,10 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
                     RcclGroup group(nc);
                     for (size_t c = 0; c < ncols; c++) {
                         const OutColumn &src = part->cols[c];
-                        const size_t nb = src.type == QE_BOOLEAN ? words_of(n_k) * 8 : width_of(src.type) * (size_t)n_k;
+                        const size_t nb = column_bytes(src.type, n_k);
                         QE_NCCL(nc.Send(src.data, nb, kNcclUint8, root, ctx->comm, ctx->copy_stream));
                         if ((any_validity >> c) & 1u)
-                            QE_NCCL(nc.Send(src.validity ? src.validity : ones, words_of(n_k) * 8, kNcclUint8, root, ctx->comm, ctx->copy_stream));
+                            QE_NCCL(nc.Send(src.validity ? src.validity : ones, bitmap_bytes(n_k), kNcclUint8, root, ctx->comm, ctx->copy_stream));
                     }
                     group.end();
                 }
@@ -767,11 +593,11 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
                         for (size_t c = 0; c < ncols; c++) {
                             OutColumn &dst = res->cols[c];
                             if (dst.type == QE_BOOLEAN)
-                                QE_NCCL(nc.Recv(staged[(size_t)k][si++].words, words_of(n) * 8, kNcclUint8, r, ctx->comm, ctx->copy_stream));
+                                QE_NCCL(nc.Recv(staged[(size_t)k][si++].words, bitmap_bytes(n), kNcclUint8, r, ctx->comm, ctx->copy_stream));
                             else
-                                QE_NCCL(nc.Recv((char *)dst.data + width_of(dst.type) * (size_t)off, width_of(dst.type) * (size_t)n, kNcclUint8, r,
+                                QE_NCCL(nc.Recv((char *)dst.data + type_width(dst.type) * (size_t)off, type_width(dst.type) * (size_t)n, kNcclUint8, r,
                                                 ctx->comm, ctx->copy_stream));
-                            if (dst.nullable) QE_NCCL(nc.Recv(staged[(size_t)k][si++].words, words_of(n) * 8, kNcclUint8, r, ctx->comm, ctx->copy_stream));
+                            if (dst.nullable) QE_NCCL(nc.Recv(staged[(size_t)k][si++].words, bitmap_bytes(n), kNcclUint8, r, ctx->comm, ctx->copy_stream));
                         }
                     }
                     group.end();
@@ -785,7 +611,7 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
                     if (src.type == QE_BOOLEAN)
                         launch_bitmap_place(ctx->copy_stream, (uint64_t *)dst.data, my_off, (const uint64_t *)src.data, n_k);
                     else
-                        QE_HIP(hipMemcpyAsync((char *)dst.data + width_of(src.type) * (size_t)my_off, src.data, width_of(src.type) * (size_t)n_k,
+                        QE_HIP(hipMemcpyAsync((char *)dst.data + type_width(src.type) * (size_t)my_off, src.data, type_width(src.type) * (size_t)n_k,
                                               hipMemcpyDeviceToDevice, ctx->copy_stream));
                     if (dst.nullable) launch_bitmap_place(ctx->copy_stream, dst.validity, my_off, src.validity ? src.validity : ones, n_k);
                 }

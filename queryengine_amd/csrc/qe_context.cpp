@@ -28,6 +28,8 @@ uint64_t DictData::next_id() {
 }
 
 // ---- pool ------------------------------------------------------------------------------
+// Every request is rounded up to whole 256-byte blocks, at least one: this is the ONE place that handles a zero-byte request
+// (an empty column, a sort of no rows), so callers pass the size they mean.
 void *Pool::alloc(size_t bytes) {
     bytes = std::max<size_t>(256, (bytes + 255) & ~size_t(255));
     auto it = free_.lower_bound(bytes);
@@ -308,13 +310,13 @@ int32_t qe_batch_create(qe_ctx *ctx, int64_t nrows, int32_t ncols, const qe_col_
             c.type = cols[j].type;
             if (c.type == QE_STRING) c.dict = cols[j].dict->d;
             size_t nb = column_bytes(c.type, nrows);
-            c.data = ctx->pool.alloc(std::max<size_t>(nb, 16));
+            c.data = ctx->pool.alloc(nb);
             b->cols.push_back(c);
             if (nb) QE_HIP(hipMemcpyAsync(c.data, cols[j].data, nb, hipMemcpyHostToDevice, ctx->stream));
             if (cols[j].validity) {
                 // also for an empty batch: nullability is part of the plan key, and the empty batch of a stream must find the
                 // plan of its schema, not compile one for a schema without nulls
-                b->cols.back().validity = (uint64_t *)ctx->pool.alloc(std::max<size_t>(bitmap_bytes(nrows), 16));
+                b->cols.back().validity = (uint64_t *)ctx->pool.alloc(bitmap_bytes(nrows));
                 if (nrows > 0)
                     QE_HIP(hipMemcpyAsync(b->cols.back().validity, cols[j].validity, bitmap_bytes(nrows),
                                           hipMemcpyHostToDevice, ctx->stream));
@@ -413,7 +415,7 @@ int32_t qe_batch_generate(qe_ctx *ctx, uint64_t seed, int64_t row_begin, int64_t
             }
             if (g.kind != QE_GEN_F64_UNIT && g.kind != QE_GEN_F64_PRICE && g.kind != QE_GEN_I64_ROWID && g.modulus == 0)
                 fail(QE_ERR_INVALID_ARG, "generator modulus must be > 0");
-            c.data = ctx->pool.alloc(std::max<size_t>(column_bytes(c.type, nrows), 16));
+            c.data = ctx->pool.alloc(column_bytes(c.type, nrows));
             if (g.null_pct > 0 && nrows > 0) c.validity = (uint64_t *)ctx->pool.alloc(bitmap_bytes(nrows));
             b->cols.push_back(c);
             launch_generate(ctx->stream, g, seed, row_begin, nrows, c.data, c.validity);

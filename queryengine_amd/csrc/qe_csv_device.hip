@@ -605,7 +605,7 @@ qe_batch *parse_on_device(qe_ctx *ctx, PoolScratch &S, const unsigned char *dev,
         Column c;
         c.type = rq.types[k];
         const size_t nb = c.type == QE_BOOLEAN ? words * 8 : (size_t)nrows * (c.type == QE_DOUBLE ? 8 : 4);
-        c.data = ctx->pool.alloc(std::max<size_t>(nb, 16));
+        c.data = ctx->pool.alloc(nb);
         if (nrows > 0) c.validity = (uint64_t *)ctx->pool.alloc(words * 8);
         if (c.type == QE_STRING) c.dict = std::make_shared<DictData>();
         b->cols.push_back(c);

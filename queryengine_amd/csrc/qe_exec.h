@@ -2,7 +2,11 @@
 //   qe_context.cpp   errors, pools, contexts, dictionaries, batches, expression handles, stream calibrations
 //   qe_api.cpp       plan cache + geometry (get_plan), the filter+project executor and its entry points
 //   qe_groupby.cpp   the global aggregate and the GROUP BY routes with their entry points
-//   qe_result.cpp    results on the device and their way to the host
+//   qe_result.cpp    results on the device: how every operator builds one (new_result, add_column, gather_columns), and
+//                    their way to the host
+//   qe_sort.cpp      ORDER BY with top-k, and the stable multi-key radix sort (RadixBuffers, SortDriver) that the join build,
+//                    the window operator and the device group finish share with it
+//   qe_comm.cpp      the RCCL exchange step and the concatenation of results
 //   qe_join.cpp      the hash equi-join of two device-resident sides, a result as the next plan's batch
 //   qe_window.cpp    window functions over a result: the sort, the boundary flags, the segmented scans
 #pragma once
@@ -48,11 +52,72 @@ inline size_t type_width(int t) {
     default: return 0;
     }
 }
-inline size_t bitmap_bytes(int64_t n) { return (size_t)((n + 63) / 64) * 8; }
+inline int64_t bitmap_words(int64_t n) { return (n + 63) / 64; }
+inline size_t bitmap_bytes(int64_t n) { return (size_t)bitmap_words(n) * 8; }
 inline size_t column_bytes(int t, int64_t n) { return t == QE_BOOLEAN ? bitmap_bytes(n) : type_width(t) * (size_t)n; }
 
 // ---- qe_result.cpp --------------------------------------------------------------------------------------
 void free_result(qe_ctx *ctx, qe_result *r);
+
+// A result under construction: whatever throws on the way, every buffer its columns hold goes back to the context's pool.
+struct ResultDeleter {
+    qe_ctx *ctx;
+    void operator()(qe_result *r) const { free_result(ctx, r); }
+};
+using ResultPtr = std::unique_ptr<qe_result, ResultDeleter>;
+inline ResultPtr own_result(qe_ctx *ctx, qe_result *r) { return ResultPtr(r, ResultDeleter{ctx}); }
+// an empty result of `count` rows (capacity = count)
+ResultPtr new_result(qe_ctx *ctx, int64_t count);
+// One more column of `nrows` rows: values and, if nullable, a validity bitmap from the pool, uninitialised.  The column is
+// pushed BEFORE its buffers are allocated, so a failing allocation leaves nothing that the result does not own.
+OutColumn &add_column(qe_ctx *ctx, qe_result *res, int type, bool nullable, const std::shared_ptr<DictData> &dict, int64_t nrows);
+// the column turned out to hold no NULL: its bitmap goes back to the pool
+void drop_validity(qe_ctx *ctx, OutColumn &c);
+// dst[j] = row rows[j] of a source column, j < nout.  Row 0xFFFFFFFF ("no row", the LEFT join's) gives a zero value and
+// validity 0; a source without bitmap reads as all valid.  dst carries a bitmap exactly when it is nullable.  max_blocks: the
+// grid cap of the launches, kGatherBlocks or kGatherBlocksWide (qe_kernels.h)
+void gather_column(qe_ctx *ctx, int type, const void *data, const uint64_t *validity, const uint32_t *rows, int64_t nout, OutColumn &dst,
+                   int max_blocks);
+// the same for every column of src_cols, into the first columns of dst (kGatherBlocks)
+void gather_columns(qe_ctx *ctx, const std::vector<OutColumn> &src_cols, const uint32_t *rows, int64_t nout, qe_result *dst);
+
+// ---- qe_sort.cpp: the stable LSD radix sort of (u64 key, u32 row) pairs -----------------------------------
+// Its scratch: two key buffers, two row buffers and the histogram words of launch_radix_pass.  The caller fills side 0 --
+// its own buffers, when it already holds the keys and rows there -- and runs the passes it needs.
+struct RadixBuffers {
+    unsigned long long *keys[2];
+    uint32_t *rows[2];
+    uint32_t *hist;
+    int64_t m;
+    int cur = 0;
+    RadixBuffers(PoolScratch &sc, int64_t m, unsigned long long *keys0 = nullptr, uint32_t *rows0 = nullptr);
+    // one stable pass over the 4 key bits at `shift`, or (shift 64 / 65) over the rows' bits in `validity`
+    void pass(hipStream_t s, int shift, const uint64_t *validity = nullptr);
+    unsigned long long *sorted_keys() const { return keys[cur]; }
+    uint32_t *sorted_rows() const { return rows[cur]; }
+};
+
+// The stable multi-key sort of a result's rows: ORDER BY, and the partition / order sort of the window operator.
+struct SortDriver {
+    qe_ctx *ctx;
+    PoolScratch &sc;
+    const qe_result *src;
+    const qe_sort_key *keys;
+    int32_t nkeys;
+    std::vector<const int *> d_ranks;   // per key: compareTo ranks of a STRING column's dictionary
+    std::vector<int> nranks;
+    std::vector<std::vector<std::vector<int32_t>>> h_ranks;   // the host tables, alive until the uploads have completed
+    unsigned long long *d_bits = nullptr;
+    int64_t radix_passes = 0;
+
+    void prepare();
+    // images of key k for m elements: of rows 0..m-1 (perm == nullptr; rows_out[i] = i unless null) or of rows perm[0..m)
+    void images(int32_t k, int64_t m, const uint32_t *perm, unsigned long long *keys_out, uint32_t *rows_out);
+    // bits that differ between the m images (a digit without such a bit is the same in every key: its pass is skipped)
+    unsigned long long varying(const unsigned long long *k, int64_t m);
+    // stable sort of the row ids in side 0 of `rb` (identity: they are 0..m-1 and are written here) by all keys
+    void sort(RadixBuffers &rb, bool identity);
+};
 
 // ---- qe_api.cpp: plans and launches -------------------------------------------------------------------------
 // What get_plan is asked for; a call site names only what it sets.

@@ -5,7 +5,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <functional>
 
 #include "qe_exec.h"
 #include "qe_kernels.h"
@@ -18,26 +17,70 @@ constexpr int kScatterWgsPerCu = 2;   // workgroups per CU of the partitioned gr
 
 qe_result *run_groupby_dense(qe_ctx *ctx, const qe_batch *batch, const std::shared_ptr<Plan> &plan, const int32_t *agg_fns, int32_t nagg);
 
+// Host arrays that asynchronous uploads read: alive until the caller has synchronised the stream.
+struct HostStaging {
+    std::vector<std::vector<unsigned long long>> w64;
+    std::vector<std::vector<int32_t>> w32;
+    std::vector<std::vector<double>> f64;
+};
+
+// One more column of `res`, uploaded from m host values (a BOOLEAN column: bitmap words) and -- when some row is NULL --
+// validity words; a column without a NULL carries no bitmap.
+void upload_column(qe_ctx *ctx, qe_result *res, const OutSpec &spec, int64_t m, const void *values, const unsigned long long *valid) {
+    OutColumn &oc = add_column(ctx, res, spec.type, valid != nullptr, spec.dict, m);
+    if (m == 0) return;
+    QE_HIP(hipMemcpyAsync(oc.data, values, column_bytes(spec.type, m), hipMemcpyHostToDevice, ctx->stream));
+    if (valid) QE_HIP(hipMemcpyAsync(oc.validity, valid, bitmap_bytes(m), hipMemcpyHostToDevice, ctx->stream));
+}
+
+// Aggregate columns of a group-by result, finished as Accumulators.kt:26-107 says: row j's {first row, (count, acc) per
+// aggregate} words come from `acc_of(j)`.
+template <typename AccOf>
+void append_aggregate_columns(qe_ctx *ctx, const CodegenOutput &cg, qe_result *res, int64_t m, AccOf acc_of, const int32_t *agg_fns, int32_t nagg,
+                              HostStaging &keep) {
+    const size_t words = (size_t)std::max<int64_t>(1, (m + 63) / 64);
+    for (int i = 0; i < nagg; i++) {
+        std::vector<double> vals((size_t)std::max<int64_t>(m, 1), 0.0);
+        std::vector<unsigned long long> valid(words, 0);
+        bool any_null = false;
+        for (int64_t j = 0; j < m; j++) {
+            const unsigned long long *e = acc_of(j);
+            const unsigned long long cnt = e[1 + 2 * cg.cnt_src[i]];
+            const unsigned long long raw = e[2 + 2 * i];
+            double v = 0.0;
+            bool ok = true;
+            switch (agg_fns[i]) {
+            case QE_AGG_COUNT: v = (double)cnt; break;                       // Accumulators.kt:26-36
+            case QE_AGG_SUM: std::memcpy(&v, &raw, 8); ok = cnt != 0; break;  // :47-53 empty => null
+            case QE_AGG_AVG: std::memcpy(&v, &raw, 8); ok = cnt != 0; if (ok) v /= (double)cnt; break;
+            default: {                                                        // MIN / MAX: undo the ordered key
+                long long key = (long long)raw;
+                long long b = key ^ ((key >> 63) & 0x7fffffffffffffffll);
+                std::memcpy(&v, &b, 8);
+                ok = cnt != 0;
+            }
+            }
+            if (ok) valid[j >> 6] |= 1ull << (j & 63);
+            else { any_null = true; v = 0.0; }
+            vals[j] = v;
+        }
+        keep.f64.push_back(std::move(vals));
+        if (any_null) keep.w64.push_back(std::move(valid));
+        upload_column(ctx, res, OutSpec{QE_DOUBLE, any_null, nullptr}, m, keep.f64.back().data(), any_null ? keep.w64.back().data() : nullptr);
+    }
+}
+
 // GroupByAggregation over arbitrary key tuples (a DOUBLE / INT64 / INT32 key, or more key combinations than a dense table
 // holds): the hashed form.  Global open-addressing table, grown (x8) and the kernel run again when it got more than half
 // full; the used entries are collected on the device, sorted by smallest row id on the host (LinkedHashMap insertion order,
 // GroupByAggregationOperator.kt:22) and finished like the dense form's (Accumulators.kt:26-107).
 // Key columns of a hashed group-by result: row j's {null bits, key words..} come from `key_of(j)`.
 template <typename KeyOf>
-void append_key_columns(qe_ctx *ctx, const CodegenOutput &cg, qe_result *res, int64_t m, KeyOf key_of,
-                        std::vector<std::vector<unsigned long long>> &keep64, std::vector<std::vector<int32_t>> &keep32) {
+void append_key_columns(qe_ctx *ctx, const CodegenOutput &cg, qe_result *res, int64_t m, KeyOf key_of, HostStaging &keep) {
     const int NK = (int)cg.keys.size();
     const size_t words = (size_t)std::max<int64_t>(1, (m + 63) / 64);
-    auto upload = [&](const void *src, size_t bytes) -> void * {
-        void *d = ctx->pool.alloc(std::max<size_t>(bytes, 16));
-        if (bytes) QE_HIP(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return d;
-    };
     for (int k = 0; k < NK; k++) {
-        OutColumn oc;
-        oc.type = cg.keys[k].type;
-        oc.dict = cg.keys[k].dict;
-        oc.dict_handle.d = oc.dict;
+        const int type = cg.keys[k].type;
         std::vector<unsigned long long> valid(words, 0), vals64((size_t)std::max<int64_t>(m, 1), 0), bits(words, 0);
         std::vector<int32_t> vals32((size_t)std::max<int64_t>(m, 1), 0);
         bool any_null = false;
@@ -50,22 +93,16 @@ void append_key_columns(qe_ctx *ctx, const CodegenOutput &cg, qe_result *res, in
             vals32[j] = (int32_t)(int64_t)kw;     // INT32 / dictionary codes
             if (kw) bits[j >> 6] |= 1ull << (j & 63);
         }
-        oc.nullable = any_null;
-        if (oc.type == QE_BOOLEAN) {
-            keep64.push_back(bits);
-            oc.data = upload(keep64.back().data(), words * 8);
-        } else if (oc.type == QE_DOUBLE || oc.type == QE_INT64) {
-            keep64.push_back(vals64);
-            oc.data = upload(keep64.back().data(), (size_t)m * 8);
+        const void *values = nullptr;
+        if (type == QE_BOOLEAN || type_width(type) == 8) {
+            keep.w64.push_back(std::move(type == QE_BOOLEAN ? bits : vals64));
+            values = keep.w64.back().data();
         } else {
-            keep32.push_back(vals32);
-            oc.data = upload(keep32.back().data(), (size_t)m * 4);
+            keep.w32.push_back(std::move(vals32));
+            values = keep.w32.back().data();
         }
-        if (any_null) {
-            keep64.push_back(valid);
-            oc.validity = (uint64_t *)upload(keep64.back().data(), words * 8);
-        }
-        res->cols.push_back(oc);
+        if (any_null) keep.w64.push_back(std::move(valid));
+        upload_column(ctx, res, cg.keys[k], m, values, any_null ? keep.w64.back().data() : nullptr);
     }
 }
 
@@ -79,8 +116,7 @@ qe_result *run_groupby_ids(qe_ctx *ctx, const qe_batch *batch, const Plan &plan,
     const int NK = (int)cg.keys.size(), BW = NK == 1 ? 2 : 3 + NK;   // single-key plans: 16-byte entries {key, state | null bits | id}
     const int64_t n = batch->nrows;
     PoolScratch temps(ctx);
-    auto talloc = [&](size_t bytes) { return temps.alloc(std::max<size_t>(bytes, 16)); };
-    uint32_t *d_ids = (uint32_t *)talloc((size_t)n * 4);
+    uint32_t *d_ids = (uint32_t *)temps.alloc((size_t)n * 4);
     hipFunction_t f_build = nullptr;
     QE_HIP(hipModuleGetFunction(&f_build, plan.kernel.module, "qe_ht_build"));
     int64_t C = plan.id_capacity > 0 ? plan.id_capacity : (1ll << 16);
@@ -88,8 +124,8 @@ qe_result *run_groupby_ids(qe_ctx *ctx, const qe_batch *batch, const Plan &plan,
     unsigned long long *d_keys = nullptr;
     double build_ms = 0.0;
     for (;;) {
-        unsigned long long *d_tab = (unsigned long long *)talloc((size_t)C * BW * 8);
-        d_keys = (unsigned long long *)talloc((size_t)C * (1 + NK) * 8);
+        unsigned long long *d_tab = (unsigned long long *)temps.alloc((size_t)C * BW * 8);
+        d_keys = (unsigned long long *)temps.alloc((size_t)C * (1 + NK) * 8);
         QE_HIP(hipMemsetAsync(d_tab, 0, (size_t)C * BW * 8, ctx->stream));
         QE_HIP(hipMemsetAsync(ctx->d_ctrl, 0, 96, ctx->stream));
         const int64_t sub_rows = plan.geo.sub_rows();
@@ -167,8 +203,7 @@ qe_result *run_groupby_ids(qe_ctx *ctx, const qe_batch *batch, const Plan &plan,
     const qe_expr *kp[1] = {&kx};
     auto dplan = get_plan(ctx, &tmp, PlanRequest{filter, exprs, nagg, agg_fns, kp, 1});
     if (dplan->cg.hashed) fail(QE_ERR_INTERNAL, "dense-id plan came out hashed");
-    std::unique_ptr<qe_result, std::function<void(qe_result *)>> r(run_groupby_dense(ctx, &tmp, dplan, agg_fns, nagg),
-                                                                   [ctx](qe_result *q) { free_result(ctx, q); });
+    const ResultPtr r = own_result(ctx, run_groupby_dense(ctx, &tmp, dplan, agg_fns, nagg));
     if (ctx->opts.profile) {   // one step = build pass + dense passes
         ctx->last_ms += build_ms;
         ctx->total_ms += build_ms;
@@ -180,12 +215,9 @@ qe_result *run_groupby_ids(qe_ctx *ctx, const qe_batch *batch, const Plan &plan,
     if (m > 0) QE_HIP(hipMemcpyAsync(rid.data(), r->cols[0].data, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (D > 0) QE_HIP(hipMemcpyAsync(hkeys.data(), d_keys, (size_t)D * (1 + NK) * 8, hipMemcpyDeviceToHost, ctx->stream));
     QE_HIP(hipStreamSynchronize(ctx->stream));
-    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [ctx](qe_result *q) { free_result(ctx, q); });
-    res->count = m;
-    res->capacity = m;
-    std::vector<std::vector<unsigned long long>> keep64;
-    std::vector<std::vector<int32_t>> keep32;
-    append_key_columns(ctx, cg, res.get(), m, [&](int64_t j) { return &hkeys[(size_t)rid[(size_t)j] * (1 + NK)]; }, keep64, keep32);
+    ResultPtr res = new_result(ctx, m);
+    HostStaging keep;
+    append_key_columns(ctx, cg, res.get(), m, [&](int64_t j) { return &hkeys[(size_t)rid[(size_t)j] * (1 + NK)]; }, keep);
     for (size_t c = 1; c < r->cols.size(); c++) {   // the aggregates move over as they are
         res->cols.push_back(r->cols[c]);
         r->cols[c].data = nullptr;
@@ -203,51 +235,31 @@ qe_result *finish_hashed_groups_on_device(qe_ctx *ctx, const CodegenOutput &cg, 
                                           const int32_t *agg_fns, int32_t nagg) {
     const int W = cg.hash_words, NK = (int)cg.keys.size();
     PoolScratch temps(ctx);
-    auto talloc = [&](size_t bytes) { return temps.alloc(std::max<size_t>(bytes, 16)); };
-    unsigned long long *keys[2] = {(unsigned long long *)talloc((size_t)m * 8), (unsigned long long *)talloc((size_t)m * 8)};
-    uint32_t *rows[2] = {(uint32_t *)talloc((size_t)m * 4), (uint32_t *)talloc((size_t)m * 4)};
-    uint32_t *hist = (uint32_t *)talloc((size_t)16 * (size_t)((m + 1023) / 1024) * 4);
-    launch_group_sort_keys(ctx->stream, d_entries, W, 2 + NK, m, keys[0], rows[0]);
+    RadixBuffers rb(temps, m);
+    launch_group_sort_keys(ctx->stream, d_entries, W, 2 + NK, m, rb.keys[0], rb.rows[0]);
     int bits = 1;
     while (bits < 62 && (1ll << bits) < nrows) bits++;
-    int cur = 0;
-    for (int shift = 0; shift < bits; shift += 4) {
-        launch_radix_pass(ctx->stream, keys[cur], rows[cur], nullptr, m, shift, hist, keys[1 - cur], rows[1 - cur]);
-        cur = 1 - cur;
-    }
-    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [ctx](qe_result *r) { free_result(ctx, r); });
-    res->count = m;
-    res->capacity = m;
-    const size_t words = (size_t)std::max<int64_t>(1, (m + 63) / 64);
+    for (int shift = 0; shift < bits; shift += 4) rb.pass(ctx->stream, shift);
+    ResultPtr res = new_result(ctx, m);
     GroupFinishArgs a{};
     a.entries = d_entries;
-    a.rows = rows[cur];
+    a.rows = rb.sorted_rows();
     a.m = m;
     a.words = W;
     a.nkeys = NK;
     a.nagg = nagg;
-    unsigned int *d_flags = (unsigned int *)talloc(64);
+    unsigned int *d_flags = (unsigned int *)temps.alloc(64);
     QE_HIP(hipMemsetAsync(d_flags, 0, 64, ctx->stream));
     a.flags = d_flags;
+    // every column gets a bitmap: which of them hold a NULL is known only after the kernel
     for (int k = 0; k < NK; k++) {
-        OutColumn oc;
-        oc.type = cg.keys[k].type;
-        oc.dict = cg.keys[k].dict;
-        oc.dict_handle.d = oc.dict;
-        const size_t bytes = oc.type == QE_BOOLEAN ? words * 8 : (oc.type == QE_DOUBLE || oc.type == QE_INT64) ? (size_t)m * 8 : (size_t)m * 4;
-        oc.data = ctx->pool.alloc(std::max<size_t>(bytes, 16));
-        oc.validity = (uint64_t *)ctx->pool.alloc(words * 8);
-        res->cols.push_back(oc);
+        const OutColumn &oc = add_column(ctx, res.get(), cg.keys[k].type, true, cg.keys[k].dict, m);
         a.key_type[k] = oc.type;
         a.key_data[k] = oc.data;
         a.key_valid[k] = (unsigned long long *)oc.validity;
     }
     for (int i = 0; i < nagg; i++) {
-        OutColumn oc;
-        oc.type = QE_DOUBLE;
-        oc.data = ctx->pool.alloc(std::max<size_t>((size_t)m * 8, 16));
-        oc.validity = (uint64_t *)ctx->pool.alloc(words * 8);
-        res->cols.push_back(oc);
+        const OutColumn &oc = add_column(ctx, res.get(), QE_DOUBLE, true, nullptr, m);
         a.agg_fn[i] = agg_fns[i];
         a.cnt_src[i] = cg.cnt_src[(size_t)i];
         a.agg_data[i] = (double *)oc.data;
@@ -258,14 +270,8 @@ qe_result *finish_hashed_groups_on_device(qe_ctx *ctx, const CodegenOutput &cg, 
     QE_HIP(hipMemcpyAsync(flags, d_flags, 64, hipMemcpyDeviceToHost, ctx->stream));
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));
-    for (int c = 0; c < NK + nagg; c++) {   // a column without a NULL carries no bitmap
-        OutColumn &oc = res->cols[(size_t)c];
-        oc.nullable = flags[c < NK ? c : 4 + (c - NK)] != 0;
-        if (!oc.nullable) {
-            ctx->pool.release(oc.validity);
-            oc.validity = nullptr;
-        }
-    }
+    for (int c = 0; c < NK + nagg; c++)   // a column without a NULL carries no bitmap
+        if (flags[c < NK ? c : 4 + (c - NK)] == 0) drop_validity(ctx, res->cols[(size_t)c]);
     return res.release();
 }
 
@@ -297,55 +303,10 @@ qe_result *finish_hashed_groups(qe_ctx *ctx, const CodegenOutput &cg, const unsi
             order.swap(tmp);
         }
     }
-    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [ctx](qe_result *r) { free_result(ctx, r); });
-    res->count = m;
-    res->capacity = m;
-    const size_t words = (size_t)std::max<int64_t>(1, (m + 63) / 64);
-    auto upload = [&](const void *src, size_t bytes) -> void * {
-        void *d = ctx->pool.alloc(std::max<size_t>(bytes, 16));
-        if (bytes) QE_HIP(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return d;
-    };
-    std::vector<std::vector<unsigned long long>> keep64;   // host staging must outlive the async copies
-    std::vector<std::vector<int32_t>> keep32;
-    append_key_columns(ctx, cg, res.get(), m, [&](int64_t j) { return &dense[(size_t)order[(size_t)j].second * W + 1]; }, keep64, keep32);
-    std::vector<std::vector<double>> keep_vals;
-    for (int i = 0; i < nagg; i++) {
-        OutColumn oc;
-        oc.type = QE_DOUBLE;
-        std::vector<double> vals((size_t)std::max<int64_t>(m, 1), 0.0);
-        std::vector<unsigned long long> valid(words, 0);
-        bool any_null = false;
-        for (int64_t j = 0; j < m; j++) {
-            const unsigned long long *e = &dense[(size_t)order[j].second * W] + ACC;   // {first row, (count, acc)..}
-            const unsigned long long cnt = e[1 + 2 * cg.cnt_src[i]];
-            const unsigned long long raw = e[2 + 2 * i];
-            double v = 0.0;
-            bool ok = true;
-            switch (agg_fns[i]) {
-            case QE_AGG_COUNT: v = (double)cnt; break;                       // Accumulators.kt:26-36
-            case QE_AGG_SUM: std::memcpy(&v, &raw, 8); ok = cnt != 0; break;  // :47-53 empty => null
-            case QE_AGG_AVG: std::memcpy(&v, &raw, 8); ok = cnt != 0; if (ok) v /= (double)cnt; break;
-            default: {                                                        // MIN / MAX: undo the ordered key
-                long long key = (long long)raw;
-                long long b = key ^ ((key >> 63) & 0x7fffffffffffffffll);
-                std::memcpy(&v, &b, 8);
-                ok = cnt != 0;
-            }
-            }
-            if (ok) valid[j >> 6] |= 1ull << (j & 63);
-            else { any_null = true; v = 0.0; }
-            vals[j] = v;
-        }
-        oc.nullable = any_null;
-        keep_vals.push_back(std::move(vals));
-        oc.data = upload(keep_vals.back().data(), (size_t)m * 8);
-        if (any_null) {
-            keep64.push_back(std::move(valid));
-            oc.validity = (uint64_t *)upload(keep64.back().data(), words * 8);
-        }
-        res->cols.push_back(oc);
-    }
+    ResultPtr res = new_result(ctx, m);
+    HostStaging keep;
+    append_key_columns(ctx, cg, res.get(), m, [&](int64_t j) { return &dense[(size_t)order[(size_t)j].second * W + 1]; }, keep);
+    append_aggregate_columns(ctx, cg, res.get(), m, [&](int64_t j) { return &dense[(size_t)order[(size_t)j].second * W + ACC]; }, agg_fns, nagg, keep);
     QE_HIP(hipStreamSynchronize(ctx->stream));
     return res.release();
 }
@@ -456,9 +417,8 @@ qe_result *run_groupby_hp(qe_ctx *ctx, const qe_batch *batch, const std::shared_
     QE_HIP(hipModuleGetFunction(&f_scatter, plan->kernel.module, "qe_gb_scatter"));
     QE_HIP(hipModuleGetFunction(&f_agg, plan->kernel.module, "qe_gb_aggregate"));
     PoolScratch temps(ctx);
-    auto talloc = [&](size_t bytes) { return temps.alloc(std::max<size_t>(bytes, 16)); };
-    uint32_t *d_counts = (uint32_t *)talloc((size_t)nchunks * P * 4);
-    unsigned long long *d_start = (unsigned long long *)talloc((size_t)(P + 1) * 8);
+    uint32_t *d_counts = (uint32_t *)temps.alloc((size_t)nchunks * P * 4);
+    unsigned long long *d_start = (unsigned long long *)temps.alloc((size_t)(P + 1) * 8);
     FusedParams p;
     fill_inputs(p, batch, *plan);
     p.nchunks = nchunks;
@@ -501,8 +461,8 @@ qe_result *run_groupby_hp(qe_ctx *ctx, const qe_batch *batch, const std::shared_
         const int rec_words = 1 + cg.nvals;
         static const bool dbg_times = std::getenv("QE_DEBUG_TIMES") != nullptr;
         const auto t_alloc0 = std::chrono::steady_clock::now();
-        if (cg.hp_line_recs) p.desc = (unsigned long long *)talloc((size_t)(m_records / cg.hp_line_recs + 2) * 128);   // whole lines + the spare line
-        else p.desc = (unsigned long long *)talloc((size_t)(m_records + 16) * 8 * rec_words);
+        if (cg.hp_line_recs) p.desc = (unsigned long long *)temps.alloc((size_t)(m_records / cg.hp_line_recs + 2) * 128);   // whole lines + the spare line
+        else p.desc = (unsigned long long *)temps.alloc((size_t)(m_records + 16) * 8 * rec_words);
         if (dbg_times)
             std::fprintf(stderr, "run_groupby_hp: record array of %.2f GB from the pool in %.1f ms\n",
                          (cg.hp_line_recs ? (double)(m_records / cg.hp_line_recs + 2) * 128 : (double)(m_records + 16) * 8 * rec_words) / 1e9,
@@ -525,7 +485,7 @@ qe_result *run_groupby_hp(qe_ctx *ctx, const qe_batch *batch, const std::shared_
                          h[1] / waves_total, h[2] / waves_total, h[3] / waves_total, h[4] / waves_total);
         }
         const int64_t cap = (int64_t)P * cg.part_groups;   // every bucket of every partition: cannot be exceeded
-        unsigned long long *d_out = (unsigned long long *)talloc((size_t)cap * HW * 8);
+        unsigned long long *d_out = (unsigned long long *)temps.alloc((size_t)cap * HW * 8);
         p.agg_partial = (double *)d_out;
         p.capacity = cap;
         p.ticket = ctx->d_ctrl;
@@ -590,9 +550,8 @@ qe_result *run_groupby_dense(qe_ctx *ctx, const qe_batch *batch, const std::shar
         QE_HIP(hipModuleGetFunction(&f_count, plan->kernel.module, "qe_gb_count"));
         QE_HIP(hipModuleGetFunction(&f_scatter, plan->kernel.module, "qe_gb_scatter"));
         PoolScratch temps(ctx);
-        auto talloc = [&](size_t bytes) { return temps.alloc(std::max<size_t>(bytes, 16)); };
-        uint32_t *d_counts = (uint32_t *)talloc((size_t)nchunks * P * 4);
-        unsigned long long *d_start = (unsigned long long *)talloc((size_t)(P + 1) * 8);
+        uint32_t *d_counts = (uint32_t *)temps.alloc((size_t)nchunks * P * 4);
+        unsigned long long *d_start = (unsigned long long *)temps.alloc((size_t)(P + 1) * 8);
         FusedParams p;
         fill_inputs(p, batch, *plan);
         p.nchunks = nchunks;
@@ -616,7 +575,7 @@ qe_result *run_groupby_dense(qe_ctx *ctx, const qe_batch *batch, const std::shar
             p.l1 = d_start;
             const int rec_words = 1 + cg.nvals;
             if (m_records >= (1ull << 32)) fail(QE_ERR_UNSUPPORTED, "partitioned GROUP BY: more than 2^32 records");
-            p.desc = (unsigned long long *)talloc((size_t)(m_records + 16) * 8 * rec_words);   // + the spare line the scatter's idle threads write
+            p.desc = (unsigned long long *)temps.alloc((size_t)(m_records + 16) * 8 * rec_words);   // + the spare line the scatter's idle threads write
             // two workgroups per CU: the 64 KiB LDS stage of the tile sort lets two share a CU (one sorts and stores while the
             // other waits for its loads)
             static const int scatter_wgs = std::getenv("QE_GB_SCATTER_WGS_PER_CU") ? std::atoi(std::getenv("QE_GB_SCATTER_WGS_PER_CU")) : kScatterWgsPerCu;
@@ -693,25 +652,12 @@ qe_result *run_groupby_dense(qe_ctx *ctx, const qe_batch *batch, const std::shar
         if (tab[(size_t)g * W] != ~0ull) order.emplace_back(tab[(size_t)g * W], g);
     std::sort(order.begin(), order.end());
     const int64_t m = (int64_t)order.size();
-    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [ctx](qe_result *r) { free_result(ctx, r); });
-    res->count = m;
-    res->capacity = m;
+    ResultPtr res = new_result(ctx, m);
     const size_t words = (size_t)std::max<int64_t>(1, (m + 63) / 64);
-    auto upload = [&](const void *src, size_t bytes) -> void * {
-        void *d = ctx->pool.alloc(std::max<size_t>(bytes, 16));
-        if (bytes) QE_HIP(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return d;
-    };
-    std::vector<std::vector<unsigned long long>> keep_words;   // host staging must outlive the async copies
-    std::vector<std::vector<int32_t>> keep_codes;
-    std::vector<std::vector<double>> keep_vals;
+    HostStaging keep;
     int64_t stride = 1;
     for (size_t k = 0; k < cg.keys.size(); k++) {
         const int domain = cg.key_domain[k];
-        OutColumn oc;
-        oc.type = cg.keys[k].type;
-        oc.dict = cg.keys[k].dict;
-        oc.dict_handle.d = oc.dict;
         std::vector<unsigned long long> valid(words, 0), bits(words, 0);
         std::vector<int32_t> codes((size_t)std::max<int64_t>(m, 1), 0);
         bool any_null = false;
@@ -722,57 +668,19 @@ qe_result *run_groupby_dense(qe_ctx *ctx, const qe_batch *batch, const std::shar
             codes[j] = code;
             if (code) bits[j >> 6] |= 1ull << (j & 63);
         }
-        oc.nullable = any_null;
-        if (oc.type == QE_BOOLEAN) {
-            keep_words.push_back(bits);
-            oc.data = upload(keep_words.back().data(), words * 8);
+        const void *values = nullptr;
+        if (cg.keys[k].type == QE_BOOLEAN) {
+            keep.w64.push_back(std::move(bits));
+            values = keep.w64.back().data();
         } else {
-            keep_codes.push_back(codes);
-            oc.data = upload(keep_codes.back().data(), (size_t)m * 4);
+            keep.w32.push_back(std::move(codes));
+            values = keep.w32.back().data();
         }
-        if (any_null) {
-            keep_words.push_back(valid);
-            oc.validity = (uint64_t *)upload(keep_words.back().data(), words * 8);
-        }
-        res->cols.push_back(oc);
+        if (any_null) keep.w64.push_back(std::move(valid));
+        upload_column(ctx, res.get(), cg.keys[k], m, values, any_null ? keep.w64.back().data() : nullptr);
         stride *= (domain + 1);
     }
-    for (int i = 0; i < nagg; i++) {
-        OutColumn oc;
-        oc.type = QE_DOUBLE;
-        std::vector<double> vals((size_t)std::max<int64_t>(m, 1), 0.0);
-        std::vector<unsigned long long> valid(words, 0);
-        bool any_null = false;
-        for (int64_t j = 0; j < m; j++) {
-            const unsigned long long *e = &tab[(size_t)order[j].second * W];
-            const unsigned long long cnt = e[1 + 2 * cg.cnt_src[i]];
-            const unsigned long long raw = e[2 + 2 * i];
-            double v = 0.0;
-            bool ok = true;
-            switch (agg_fns[i]) {
-            case QE_AGG_COUNT: v = (double)cnt; break;                       // Accumulators.kt:26-36
-            case QE_AGG_SUM: std::memcpy(&v, &raw, 8); ok = cnt != 0; break;  // :47-53 empty => null
-            case QE_AGG_AVG: std::memcpy(&v, &raw, 8); ok = cnt != 0; if (ok) v /= (double)cnt; break;
-            default: {                                                        // MIN / MAX: undo the ordered key
-                long long key = (long long)raw;
-                long long b = key ^ ((key >> 63) & 0x7fffffffffffffffll);
-                std::memcpy(&v, &b, 8);
-                ok = cnt != 0;
-            }
-            }
-            if (ok) valid[j >> 6] |= 1ull << (j & 63);
-            else { any_null = true; v = 0.0; }
-            vals[j] = v;
-        }
-        oc.nullable = any_null;
-        keep_vals.push_back(vals);
-        oc.data = upload(keep_vals.back().data(), (size_t)m * 8);
-        if (any_null) {
-            keep_words.push_back(valid);
-            oc.validity = (uint64_t *)upload(keep_words.back().data(), words * 8);
-        }
-        res->cols.push_back(oc);
-    }
+    append_aggregate_columns(ctx, cg, res.get(), m, [&](int64_t j) { return &tab[(size_t)order[(size_t)j].second * W]; }, agg_fns, nagg, keep);
     QE_HIP(hipStreamSynchronize(ctx->stream));
     return res.release();
 }

@@ -101,7 +101,7 @@ JoinKeyCols key_columns(qe_ctx *ctx, PoolScratch &sc, const Side &side, const in
         if (c.dict.get() == &bd && bd.index.size() == bd.entries.size()) continue;   // the build dictionary itself, no duplicates: codes as they are
         std::vector<int32_t> table(c.dict->entries.size());
         for (size_t i = 0; i < table.size(); i++) table[i] = bd.find(c.dict->entries[i]);
-        int *d = (int *)sc.alloc(std::max<size_t>(table.size() * 4, 16));
+        int *d = (int *)sc.alloc(table.size() * 4);
         tables.push_back(std::move(table));
         if (!tables.back().empty())
             QE_HIP(hipMemcpyAsync(d, tables.back().data(), tables.back().size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -130,13 +130,12 @@ qe_join_table *build_table(qe_ctx *ctx, const qe_join_input *in, const int32_t *
     ba.kc = key_columns(ctx, sc, t->build, key_cols, nkeys, t->build, t->key_cols, tables);
     ba.n = n;
     ba.mask = t->mask;
-    unsigned long long *kbuf[2] = {(unsigned long long *)sc.alloc(std::max<size_t>((size_t)n * 8, 16)), (unsigned long long *)sc.alloc(std::max<size_t>((size_t)n * 8, 16))};
-    uint32_t *rbuf[2] = {(uint32_t *)sc.alloc(std::max<size_t>((size_t)n * 4, 16)), (uint32_t *)sc.alloc(std::max<size_t>((size_t)n * 4, 16))};
+    RadixBuffers rb(sc, n);
     unsigned long long *img[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < nkeys; k++) img[k] = ba.img[k] = (unsigned long long *)sc.alloc(std::max<size_t>((size_t)n * 8, 16));
-    ba.hash = kbuf[0];
-    ba.rows = rbuf[0];
-    ba.valid_words = (unsigned long long *)sc.alloc(std::max<size_t>(bitmap_bytes(n), 16));
+    for (int k = 0; k < nkeys; k++) img[k] = ba.img[k] = (unsigned long long *)sc.alloc((size_t)n * 8);
+    ba.hash = rb.keys[0];
+    ba.rows = rb.rows[0];
+    ba.valid_words = (unsigned long long *)sc.alloc(bitmap_bytes(n));
     ba.nvalid = (unsigned long long *)sc.alloc(16);
     QE_HIP(hipMemsetAsync(ba.nvalid, 0, 16, ctx->stream));
     launch_join_build_keys(ctx->stream, ba);
@@ -154,26 +153,18 @@ qe_join_table *build_table(qe_ctx *ctx, const qe_join_input *in, const int32_t *
 
     // stable LSD radix sort of (hash, row) on the digits that cover the directory bits; then the rows without a key go
     // behind the others (one pass on their bit).  Entries with equal hashes (so: equal keys) stay in build-row order.
-    int cur = 0;
     if (n > 0) {
-        uint32_t *hist = (uint32_t *)sc.alloc((size_t)((n + 1023) / 1024) * 16 * 4);
         const int ndigits = (dbits + 3) / 4;
-        for (int shift = 64 - 4 * ndigits; shift < 64; shift += 4) {
-            launch_radix_pass(ctx->stream, kbuf[cur], rbuf[cur], nullptr, n, shift, hist, kbuf[cur ^ 1], rbuf[cur ^ 1]);
-            cur ^= 1;
-        }
-        if (t->m < n) {
-            launch_radix_pass(ctx->stream, kbuf[cur], rbuf[cur], (const uint64_t *)ba.valid_words, n, 65, hist, kbuf[cur ^ 1], rbuf[cur ^ 1]);
-            cur ^= 1;
-        }
+        for (int shift = 64 - 4 * ndigits; shift < 64; shift += 4) rb.pass(ctx->stream, shift);
+        if (t->m < n) rb.pass(ctx->stream, 65, (const uint64_t *)ba.valid_words);
     }
     t->dir = (uint32_t *)ctx->pool.alloc(((size_t)1 << dbits) * 4 + 16);
-    launch_join_directory(ctx->stream, kbuf[cur], t->m, dbits, t->dir);
-    t->rows = (uint32_t *)ctx->pool.alloc(std::max<size_t>((size_t)t->m * 4, 16));
-    if (t->m > 0) QE_HIP(hipMemcpyAsync(t->rows, rbuf[cur], (size_t)t->m * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    launch_join_directory(ctx->stream, rb.sorted_keys(), t->m, dbits, t->dir);
+    t->rows = (uint32_t *)ctx->pool.alloc((size_t)t->m * 4);
+    if (t->m > 0) QE_HIP(hipMemcpyAsync(t->rows, rb.sorted_rows(), (size_t)t->m * 4, hipMemcpyDeviceToDevice, ctx->stream));
     for (int k = 0; k < nkeys; k++) {
-        t->img[k] = (unsigned long long *)ctx->pool.alloc(std::max<size_t>((size_t)t->m * 8, 16));
-        launch_gather_rows(ctx->stream, 8, img[k], rbuf[cur], t->m, t->img[k]);
+        t->img[k] = (unsigned long long *)ctx->pool.alloc((size_t)t->m * 8);
+        launch_gather_rows(ctx->stream, 8, img[k], rb.sorted_rows(), t->m, t->img[k]);
     }
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));
@@ -215,9 +206,9 @@ qe_result *probe_table(qe_ctx *ctx, const qe_join_table *t, const qe_join_input 
     pa.n = n;
     pa.join_type = join_type;
     const int64_t nblocks = join_probe_blocks(n);
-    pa.cnt = (uint32_t *)sc.alloc(std::max<size_t>((size_t)n * 4, 16));
-    if (pairs) pa.first = (uint32_t *)sc.alloc(std::max<size_t>((size_t)n * 4, 16));
-    pa.blocksum = (unsigned long long *)sc.alloc(std::max<size_t>((size_t)nblocks * 8, 16));
+    pa.cnt = (uint32_t *)sc.alloc((size_t)n * 4);
+    if (pairs) pa.first = (uint32_t *)sc.alloc((size_t)n * 4);
+    pa.blocksum = (unsigned long long *)sc.alloc((size_t)nblocks * 8);
     unsigned long long *d_ctl = (unsigned long long *)sc.alloc(16);   // [0] total, [1] longest walk (u32)
     pa.longest = (uint32_t *)(d_ctl + 1);
     QE_HIP(hipMemsetAsync(d_ctl, 0, 16, ctx->stream));
@@ -230,25 +221,15 @@ qe_result *probe_table(qe_ctx *ctx, const qe_join_table *t, const qe_join_input 
     const int64_t total = (int64_t)h_ctl[0];   // at most 2^32 rows of at most 2^32 matches: fits; an output too large for the
                                                // device is reported by the pool below (QE_ERR_OOM)
 
-    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [ctx](qe_result *r) { free_result(ctx, r); });
-    res->count = res->capacity = total;
+    ResultPtr res = new_result(ctx, total);
     pa.total = (unsigned long long)total;
-    pa.prow_out = (uint32_t *)sc.alloc(std::max<size_t>((size_t)total * 4, 16));
-    if (pairs) pa.brow_out = (uint32_t *)sc.alloc(std::max<size_t>((size_t)total * 4, 16));
+    pa.prow_out = (uint32_t *)sc.alloc((size_t)total * 4);
+    if (pairs) pa.brow_out = (uint32_t *)sc.alloc((size_t)total * 4);
     launch_join_write(ctx->stream, pa);
 
     auto emit = [&](const SideCol &src, const uint32_t *rows, bool force_nullable) {
-        res->cols.emplace_back();
-        OutColumn &oc = res->cols.back();
-        oc.type = src.type;
-        oc.dict = src.dict;
-        oc.dict_handle.d = src.dict;
-        oc.nullable = force_nullable || src.validity != nullptr;
-        oc.data = ctx->pool.alloc(std::max<size_t>(column_bytes(src.type, total), 16));
-        if (oc.nullable) oc.validity = (uint64_t *)ctx->pool.alloc(std::max<size_t>(bitmap_bytes(total), 16));
-        if (src.type == QE_BOOLEAN) launch_join_gather_bits(ctx->stream, (const uint64_t *)src.data, rows, total, (uint64_t *)oc.data);
-        else launch_join_gather(ctx->stream, (int)type_width(src.type), src.data, rows, total, oc.data);
-        if (oc.nullable) launch_join_gather_bits(ctx->stream, src.validity, rows, total, oc.validity);
+        OutColumn &oc = add_column(ctx, res.get(), src.type, force_nullable || src.validity != nullptr, src.dict, total);
+        gather_column(ctx, src.type, src.data, src.validity, rows, total, oc, kGatherBlocksWide);
     };
     for (int32_t i = 0; i < nprobe_out; i++) emit(side.cols[(size_t)probe_out[i]], pa.prow_out, false);
     for (int32_t i = 0; i < nbuild_out; i++) emit(t->build.cols[(size_t)build_out[i]], pa.brow_out, join_type == QE_JOIN_LEFT);

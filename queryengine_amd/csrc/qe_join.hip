@@ -11,8 +11,8 @@
 //         writes (probe row, build row) pairs at the scanned offsets.  The order of the output is therefore the order of
 //         a nested loop with the probe side outside, whatever the order in which the waves run; the only atomics are an
 //         integer add (rows with a key) and an integer max (longest bucket), both independent of arrival order.
-// GATHER  one kernel per output column through the pair lists; build row 0xFFFFFFFF ("none", LEFT) gives a zeroed value
-//         and validity 0.
+// GATHER  one launch of the shared gathers (qe_kernels.hip) per output column through the pair lists; build row 0xFFFFFFFF
+//         ("none", LEFT) gives a zeroed value and validity 0.
 #include <hip/hip_runtime.h>
 
 #include "qe_kernels.h"
@@ -251,30 +251,6 @@ __global__ void __launch_bounds__(256) join_write_kernel(const JoinProbeArgs a) 
         }
 }
 
-// ---- gathers through a pair list --------------------------------------------------------------------------------------------
-template <typename T> __global__ void __launch_bounds__(256) join_gather_kernel(const T *src, const u32 *rows, i64 n, T *out) {
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
-        const u32 r = rows[j];
-        out[j] = r == kNone ? (T)0 : src[r];
-    }
-}
-
-// src == null: a column without bitmap (every row valid): the bit says whether there is a row at all
-__global__ void __launch_bounds__(256) join_gather_bits_kernel(const u64 *src, const u32 *rows, i64 n, u64 *out) {
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    const i64 padded = (n + 63) & ~63ll;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < padded; j += stride) {
-        bool b = false;
-        if (j < n) {
-            const u32 r = rows[j];
-            b = r != kNone && (!src || jbit_at(src, (i64)r));
-        }
-        const u64 w = __ballot(b);
-        if ((threadIdx.x & 63) == 0) out[j >> 6] = w;
-    }
-}
-
 inline unsigned capped_blocks(i64 n, i64 cap) {
     const i64 blocks = (n + 255) / 256;
     return (unsigned)(blocks < cap ? blocks : cap);
@@ -306,18 +282,6 @@ void launch_join_scan(hipStream_t s, unsigned long long *blocksum, int64_t nbloc
 void launch_join_write(hipStream_t s, const JoinProbeArgs &a) {
     if (a.n <= 0 || a.total == 0) return;
     hipLaunchKernelGGL(join_write_kernel, dim3((unsigned)join_probe_blocks(a.n)), dim3(256), 0, s, a);
-}
-
-void launch_join_gather(hipStream_t s, int width, const void *src, const uint32_t *rows, int64_t n, void *out) {
-    if (n <= 0) return;
-    const dim3 g(capped_blocks(n, 16384));
-    if (width == 8) hipLaunchKernelGGL(join_gather_kernel<u64>, g, dim3(256), 0, s, (const u64 *)src, rows, (i64)n, (u64 *)out);
-    else hipLaunchKernelGGL(join_gather_kernel<u32>, g, dim3(256), 0, s, (const u32 *)src, rows, (i64)n, (u32 *)out);
-}
-
-void launch_join_gather_bits(hipStream_t s, const uint64_t *src, const uint32_t *rows, int64_t n, uint64_t *out) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(join_gather_bits_kernel, dim3(capped_blocks(n, 16384)), dim3(256), 0, s, (const u64 *)src, rows, (i64)n, (u64 *)out);
 }
 
 }  // namespace qe

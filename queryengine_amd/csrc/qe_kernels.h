@@ -89,8 +89,6 @@ void launch_select_count(hipStream_t s, const unsigned long long *keys, int64_t 
 // row ids of the candidates in row order; offsets = exclusive scan of counts; at most `capacity` ids are written
 void launch_select_compact(hipStream_t s, const unsigned long long *keys, int64_t n, const SelectState *state, const uint32_t *counts,
                            const uint32_t *offsets, uint32_t *rows_out, int64_t capacity);
-void launch_gather_rows(hipStream_t s, int width, const void *src, const uint32_t *rows, int64_t n, void *out);
-void launch_gather_bits_rows(hipStream_t s, const uint64_t *src, const uint32_t *rows, int64_t n, uint64_t *out);
 
 // ---- hash equi-join (qe_join.hip) ----
 // the key columns of one side; the image of a key column is the u64 two equal values share
@@ -140,10 +138,6 @@ int64_t join_probe_blocks(int64_t n);       // entries of blocksum
 void launch_join_count(hipStream_t s, const JoinProbeArgs &a);
 void launch_join_scan(hipStream_t s, unsigned long long *blocksum, int64_t nblocks, unsigned long long *total);
 void launch_join_write(hipStream_t s, const JoinProbeArgs &a);
-// out[j] = src[rows[j]], or zero for row 0xFFFFFFFF; width 4 or 8
-void launch_join_gather(hipStream_t s, int width, const void *src, const uint32_t *rows, int64_t n, void *out);
-// bit j of out = bit rows[j] of src (src null: 1), 0 for row 0xFFFFFFFF; whole words are written
-void launch_join_gather_bits(hipStream_t s, const uint64_t *src, const uint32_t *rows, int64_t n, uint64_t *out);
 
 // ---- window functions over a sorted result (qe_window.hip) ----
 constexpr int kWinTileRows = 2048;    // T: rows of one scan tile (4 waves x 8 words of 64 rows)
@@ -188,6 +182,15 @@ void launch_win_rank(hipStream_t s, const uint32_t *start, const uint32_t *first
 // width 8 / 4, or 0 for a bitmap column; src_valid null = every source row valid
 void launch_win_shift(hipStream_t s, int width, const void *src, const uint64_t *src_valid, const uint32_t *start, int64_t n,
                       int64_t delta, void *out, uint64_t *out_valid);
+
+// ---- gathers through u32 row ids (qe_kernels.hip): ORDER BY, window, join, per-node ----
+// grid caps, in blocks of 256 threads: every caller's, and the join's output columns (with the narrow cap the probe was 0.4 to
+// 0.6 % slower than before in every interleaved run, with the wide one it is not: profiles/result_builder_refactor_summary.txt)
+constexpr int kGatherBlocks = 8192, kGatherBlocksWide = 16384;
+// out[j] = src[rows[j]], or zero for row 0xFFFFFFFF ("no row"); width 4 or 8
+void launch_gather_rows(hipStream_t s, int width, const void *src, const uint32_t *rows, int64_t n, void *out, int max_blocks = kGatherBlocks);
+// bit j of out = bit rows[j] of src (src null: 1), 0 for row 0xFFFFFFFF; whole words are written
+void launch_gather_bits_rows(hipStream_t s, const uint64_t *src, const uint32_t *rows, int64_t n, uint64_t *out, int max_blocks = kGatherBlocks);
 
 // place nbits bits of src at bit offset dst_bit_offset of dst (bitmap words; concatenation of results / gather)
 void launch_bitmap_place(hipStream_t s, uint64_t *dst, int64_t dst_bit_offset, const uint64_t *src, int64_t nbits);

@@ -1,6 +1,8 @@
 // qe_kernels.hip -- precompiled gfx950 kernels that are not plan-specific:
 // the synthetic column generator, byte->bitmap packing of nullable/boolean
-// outputs, and the streaming-read calibration kernel used for the roofline.
+// outputs, the streaming-read calibration kernel used for the roofline, and
+// the support kernels the operators share: bitmap placement, the gathers
+// through row ids, the hashed group-by's table and finish kernels.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
@@ -306,6 +308,47 @@ void launch_bitmap_place(hipStream_t s, uint64_t *dst, int64_t dst_bit_offset, c
     const int64_t blocks = (words + 255) / 256;
     hipLaunchKernelGGL(bitmap_place_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, (u64 *)dst,
                        (i64)dst_bit_offset, (const u64 *)src, (i64)nbits);
+}
+
+// ---- gathers through u32 row ids (ORDER BY, the window operator, the join's pair lists, the per-node executor) --------------
+// Row 0xFFFFFFFF is "no row" (the build side of an unmatched LEFT join row): a zero value, a zero bit.  Sorted row ids and
+// selection vectors never hold it.  The grid is capped at max_blocks blocks of 256 threads, a stride loop beyond.
+constexpr u32 kNoRow = 0xFFFFFFFFu;
+
+template <typename T> __global__ void __launch_bounds__(256) gather_rows_kernel(const T *src, const u32 *rows, i64 n, T *out) {
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
+        const u32 r = rows[j];
+        out[j] = r == kNoRow ? (T)0 : src[r];
+    }
+}
+void launch_gather_rows(hipStream_t s, int width, const void *src, const uint32_t *rows, int64_t n, void *out, int max_blocks) {
+    if (n <= 0) return;
+    const i64 blocks = (n + 255) / 256;
+    const dim3 g((unsigned)(blocks < max_blocks ? blocks : max_blocks));
+    if (width == 8) hipLaunchKernelGGL(gather_rows_kernel<u64>, g, dim3(256), 0, s, (const u64 *)src, rows, (i64)n, (u64 *)out);
+    else hipLaunchKernelGGL(gather_rows_kernel<u32>, g, dim3(256), 0, s, (const u32 *)src, rows, (i64)n, (u32 *)out);
+}
+
+// src == null: a column without bitmap (every row valid): the bit says whether there is a row at all
+__global__ void __launch_bounds__(256) gather_bits_rows_kernel(const u64 *src, const u32 *rows, i64 n, u64 *out) {
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    const i64 padded = (n + 63) & ~63ll;
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < padded; j += stride) {
+        bool b = false;
+        if (j < n) {
+            const u32 r = rows[j];
+            b = r != kNoRow && (!src || ((src[r >> 6] >> (r & 63)) & 1ull));
+        }
+        const u64 w = __ballot(b);
+        if ((threadIdx.x & 63) == 0) out[j >> 6] = w;
+    }
+}
+void launch_gather_bits_rows(hipStream_t s, const uint64_t *src, const uint32_t *rows, int64_t n, uint64_t *out, int max_blocks) {
+    if (n <= 0) return;
+    const i64 blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(gather_bits_rows_kernel, dim3((unsigned)(blocks < max_blocks ? blocks : max_blocks)), dim3(256), 0, s,
+                       (const u64 *)src, rows, (i64)n, (u64 *)out);
 }
 
 // ---- hashed group-by: table initialisation and collection of the used entries ---------------------------------------------

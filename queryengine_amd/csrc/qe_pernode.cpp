@@ -21,6 +21,8 @@
 #include <cmath>
 #include <functional>
 
+#include "qe_exec.h"
+#include "qe_kernels.h"
 #include "qe_pernode_kernels.h"
 
 namespace qe {
@@ -42,9 +44,7 @@ struct Vec {
     bool indexed = false;  // data = the BATCH column, to be read through the current domain's row ids (selection vector)
 };
 
-size_t width_of(int t) { return (t == QE_DOUBLE || t == QE_INT64) ? 8 : 4; }
 int kernel_type(int t) { return t == QE_STRING ? QE_INT32 : t; }
-int64_t words_of(int64_t n) { return (n + 63) / 64; }
 
 struct Exec {
     qe_ctx *ctx;
@@ -68,7 +68,7 @@ struct Exec {
         v.dict = b.dict;
         if (b.type == QE_BOOLEAN) {
             v.data = alloc_words();
-            pn::gather_bits(s, (const uint64_t *)b.data.get(), (const uint32_t *)ids.get(), (uint64_t *)v.data.get(), n);
+            launch_gather_bits_rows(s, (const uint64_t *)b.data.get(), (const uint32_t *)ids.get(), n, (uint64_t *)v.data.get());
         } else {
             v.data = alloc_col(b.type);
             pn::GatherArgs ga{};
@@ -76,13 +76,13 @@ struct Exec {
             ga.m = n;
             ga.src[0] = b.data.get();
             ga.dst[0] = v.data.get();
-            ga.width[0] = (int)width_of(b.type);
+            ga.width[0] = (int)type_width(b.type);
             ga.ncols = 1;
             pn::gather_multi(s, ga);
         }
         if (b.valid) {
             v.valid = alloc_words();
-            pn::gather_bits(s, (const uint64_t *)b.valid.get(), (const uint32_t *)ids.get(), (uint64_t *)v.valid.get(), n);
+            launch_gather_bits_rows(s, (const uint64_t *)b.valid.get(), (const uint32_t *)ids.get(), n, (uint64_t *)v.valid.get());
         }
         return v;
     }
@@ -106,11 +106,11 @@ struct Exec {
             v.data = alloc_col(base[j].type);
             ga.src[ga.ncols] = base[j].data.get();
             ga.dst[ga.ncols] = v.data.get();
-            ga.width[ga.ncols] = (int)width_of(base[j].type);
+            ga.width[ga.ncols] = (int)type_width(base[j].type);
             if (++ga.ncols == 8) flush();
             if (base[j].valid) {
                 v.valid = alloc_words();
-                pn::gather_bits(s, (const uint64_t *)base[j].valid.get(), (const uint32_t *)ids.get(), (uint64_t *)v.valid.get(), n);
+                launch_gather_bits_rows(s, (const uint64_t *)base[j].valid.get(), (const uint32_t *)ids.get(), n, (uint64_t *)v.valid.get());
             }
         }
         flush();
@@ -151,18 +151,18 @@ struct Exec {
             c.dict = v.dict;
             if (v.type == QE_BOOLEAN) {
                 c.data = alloc_words();
-                pn::gather_bits(s, (const uint64_t *)v.data.get(), r, (uint64_t *)c.data.get(), m);
+                launch_gather_bits_rows(s, (const uint64_t *)v.data.get(), r, m, (uint64_t *)c.data.get());
             } else {
                 c.data = alloc_col(v.type);
                 ga.src[ga.ncols] = v.data.get();
                 ga.dst[ga.ncols] = c.data.get();
-                ga.width[ga.ncols] = (int)width_of(v.type);
+                ga.width[ga.ncols] = (int)type_width(v.type);
                 keep_alive.push_back(v.data);   // the source stays allocated until its gather has been launched
                 if (++ga.ncols == 8) flush();
             }
             if (v.valid) {
                 c.valid = alloc_words();
-                pn::gather_bits(s, (const uint64_t *)v.valid.get(), r, (uint64_t *)c.valid.get(), m);
+                launch_gather_bits_rows(s, (const uint64_t *)v.valid.get(), r, m, (uint64_t *)c.valid.get());
             }
             v = c;
         }
@@ -170,12 +170,12 @@ struct Exec {
     }
 
     Buf alloc(size_t bytes) {
-        void *p = ctx->pool.alloc(std::max<size_t>(bytes, 16));
+        void *p = ctx->pool.alloc(bytes);
         qe_ctx *c = ctx;
         return Buf(p, [c](void *q) { c->pool.release(q); });
     }
-    Buf alloc_col(int type) { return alloc(width_of(type) * (size_t)n); }
-    Buf alloc_words() { return alloc((size_t)words_of(n) * 8); }
+    Buf alloc_col(int type) { return alloc(type_width(type) * (size_t)n); }   // value columns only: a BOOLEAN is alloc_words()
+    Buf alloc_words() { return alloc(bitmap_bytes(n)); }
 
     pn::Opnd opnd(const Vec &v) {
         pn::Opnd o;
@@ -193,7 +193,7 @@ struct Exec {
         r.scalar = false;
         if (v.type == QE_BOOLEAN) {
             r.data = alloc_words();
-            pn::word_fill(s, v.i ? ~0ull : 0ull, (uint64_t *)r.data.get(), words_of(n));
+            pn::word_fill(s, v.i ? ~0ull : 0ull, (uint64_t *)r.data.get(), bitmap_words(n));
         } else {
             r.data = alloc_col(v.type);
             pn::fill(s, kernel_type(v.type), opnd(v), r.data.get(), n);
@@ -205,7 +205,7 @@ struct Exec {
         if (!a) return b;
         if (!b) return a;
         Buf r = alloc_words();
-        pn::word_op(s, pn::W_AND, (const uint64_t *)a.get(), (const uint64_t *)b.get(), (uint64_t *)r.get(), words_of(n));
+        pn::word_op(s, pn::W_AND, (const uint64_t *)a.get(), (const uint64_t *)b.get(), (uint64_t *)r.get(), bitmap_words(n));
         return r;
     }
 
@@ -214,7 +214,7 @@ struct Exec {
     Buf lookup(const std::vector<int32_t> &table, const Vec &codes) {
         auto host = std::make_shared<std::vector<int32_t>>(table);
         keep_tables.push_back(host);
-        Buf dev = alloc(std::max<size_t>(host->size() * 4, 16));
+        Buf dev = alloc(host->size() * 4);
         if (!host->empty()) QE_HIP(hipMemcpyAsync(dev.get(), host->data(), host->size() * 4, hipMemcpyHostToDevice, s));
         Buf out = alloc_col(QE_INT32);
         pn::lookup_codes(s, (const int32_t *)dev.get(), (int32_t)host->size(), (const int32_t *)codes.data.get(), (int32_t *)out.get(), n);
@@ -225,7 +225,7 @@ struct Exec {
 
     Buf ones() {
         Buf r = alloc_words();
-        pn::word_fill(s, ~0ull, (uint64_t *)r.get(), words_of(n));
+        pn::word_fill(s, ~0ull, (uint64_t *)r.get(), bitmap_words(n));
         return r;
     }
 
@@ -370,7 +370,7 @@ struct Exec {
                 const int w = cmp == pn::C_EQ ? pn::W_XNOR : cmp == pn::C_NE ? pn::W_XOR : cmp == pn::C_LT ? pn::W_NOTAND
                             : cmp == pn::C_LE ? pn::W_NOTOR : cmp == pn::C_GT ? pn::W_ANDNOT : pn::W_ORNOT;
                 r.data = alloc_words();
-                pn::word_op(s, w, (const uint64_t *)x.data.get(), (const uint64_t *)y.data.get(), (uint64_t *)r.data.get(), words_of(n));
+                pn::word_op(s, w, (const uint64_t *)x.data.get(), (const uint64_t *)y.data.get(), (uint64_t *)r.data.get(), bitmap_words(n));
                 return r;
             }
             if (a.scalar && b.scalar) a = materialize(a);
@@ -382,7 +382,7 @@ struct Exec {
             Vec a = materialize(eval(e, nd.ops[0]));
             r.valid = a.valid;
             r.data = alloc_words();
-            pn::word_not(s, (const uint64_t *)a.data.get(), (uint64_t *)r.data.get(), words_of(n));
+            pn::word_not(s, (const uint64_t *)a.data.get(), (uint64_t *)r.data.get(), bitmap_words(n));
             return r;
         }
         case QE_FN_AND: case QE_FN_OR: {
@@ -391,7 +391,7 @@ struct Exec {
             if (a.valid || b.valid) r.valid = alloc_words();
             pn::kleene(s, nd.fn == QE_FN_AND, (const uint64_t *)a.data.get(), (const uint64_t *)a.valid.get(),
                        (const uint64_t *)b.data.get(), (const uint64_t *)b.valid.get(), (uint64_t *)r.data.get(),
-                       (uint64_t *)r.valid.get(), words_of(n));
+                       (uint64_t *)r.valid.get(), bitmap_words(n));
             return r;
         }
         case QE_FN_IF: {   // Interpreter.kt:46-53: null condition -> null; both branches evaluated, then selected
@@ -436,7 +436,7 @@ struct Exec {
                 Vec tt = materialize(t), ff = materialize(f);
                 r.data = alloc_words();
                 pn::select_words(s, (const uint64_t *)cond.get(), (const uint64_t *)tt.data.get(), (const uint64_t *)ff.data.get(),
-                                 (uint64_t *)r.data.get(), words_of(n));
+                                 (uint64_t *)r.data.get(), bitmap_words(n));
             } else {
                 r.data = alloc_col(nd.type);
                 pn::select(s, kernel_type(nd.type), (const uint64_t *)cond.get(), opnd(t), opnd(f), r.data.get(), n);
@@ -445,7 +445,7 @@ struct Exec {
                 Buf kt = t.valid ? t.valid : ones(), kf = f.valid ? f.valid : ones();
                 Buf sel = alloc_words();
                 pn::select_words(s, (const uint64_t *)cond.get(), (const uint64_t *)kt.get(), (const uint64_t *)kf.get(),
-                                 (uint64_t *)sel.get(), words_of(n));
+                                 (uint64_t *)sel.get(), bitmap_words(n));
                 r.valid = and_valid(c.valid, sel);
             } else {
                 r.valid = c.valid;
@@ -485,13 +485,7 @@ qe_result *run_per_node(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filte
         e.dict = c.dict;
         x.env.push_back(e);          // not gathered yet
     }
-    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [](qe_result *r) {
-        for (auto &c : r->cols) {
-            c.hold_data.reset();
-            c.hold_valid.reset();
-        }
-        delete r;
-    });
+    ResultPtr res = new_result(ctx, 0);   // (its columns share their buffers with the executor's temporaries: hold_data / hold_valid)
     int64_t m = batch->nrows;
     // A value column that the whole plan uses exactly once, as a direct operand of an arithmetic or comparison node, is never
     // gathered into a narrowed domain: the node reads it through the row ids (cfg 2: `a + b` after the filter -- 0.8 GB less
@@ -539,7 +533,7 @@ qe_result *run_per_node(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filte
             Buf keep = x.and_valid(k.data, k.valid);              // value & known (FilterOperator.kt:20)
             acc = x.and_valid(acc, keep);
             // 2. kept rows of the current domain
-            const int64_t nw = words_of(x.n);
+            const int64_t nw = bitmap_words(x.n);
             Buf counts = x.alloc((size_t)nw * 4), offsets = x.alloc((size_t)nw * 4), sums = x.alloc((size_t)((nw + 1023) / 1024) * 4 + 16);
             pn::word_popcounts(x.s, (const uint64_t *)acc.get(), nullptr, x.n, (uint32_t *)counts.get(), nw);
             pn::exclusive_scan_u32(x.s, (const uint32_t *)counts.get(), (uint32_t *)offsets.get(), (uint32_t *)sums.get(), nw, d_total);
@@ -596,9 +590,9 @@ qe_result *run_per_node(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filte
                     }
                 return b;
             };
-            const size_t dbytes = v.type == QE_BOOLEAN ? (size_t)words_of(m) * 8 : width_of(v.type) * (size_t)m;
+            const size_t dbytes = column_bytes(v.type, m);
             oc.hold_data = owned(v.data, dbytes);
-            oc.hold_valid = owned(v.valid, (size_t)words_of(m) * 8);
+            oc.hold_valid = owned(v.valid, bitmap_bytes(m));
             oc.data = oc.hold_data.get();
             oc.validity = (uint64_t *)oc.hold_valid.get();
         }

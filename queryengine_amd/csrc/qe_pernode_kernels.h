@@ -54,8 +54,6 @@ struct GatherArgs {
     long long m;
 };
 void gather_multi(hipStream_t s, const GatherArgs &a);
-void gather(hipStream_t s, int type, const void *src, const uint32_t *idx, void *out, int64_t m);
-void gather_bits(hipStream_t s, const uint64_t *src, const uint32_t *idx, uint64_t *out, int64_t m);
 // out[i] = table[codes[i]] (a code outside the table -- the garbage under a NULL -- reads as -1): string ranks / code remaps
 void lookup_codes(hipStream_t s, const int32_t *table, int32_t ntable, const int32_t *codes, int32_t *out, int64_t n);
 

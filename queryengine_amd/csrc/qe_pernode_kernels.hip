@@ -662,34 +662,6 @@ void gather_multi(hipStream_t s, const GatherArgs &a) {
     hipLaunchKernelGGL(k_gather_multi, dim3(grid_for((a.m + 3) / 4, 256, 256 * 8)), dim3(256), 0, s, a);
 }
 
-template <typename T> __global__ void __launch_bounds__(256) k_gather(const T *src, const u32 *idx, T *out, i64 m) {
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += stride) out[j] = src[idx[j]];
-}
-void gather(hipStream_t s, int type, const void *src, const uint32_t *idx, void *out, int64_t m) {
-    if (m <= 0) return;
-    const int g = grid_for(m);
-    if (type == QE_DOUBLE || type == QE_INT64) hipLaunchKernelGGL(k_gather<u64>, dim3(g), dim3(256), 0, s, (const u64 *)src, idx, (u64 *)out, (i64)m);
-    else hipLaunchKernelGGL(k_gather<u32>, dim3(g), dim3(256), 0, s, (const u32 *)src, idx, (u32 *)out, (i64)m);
-}
-__global__ void __launch_bounds__(256) k_gather_bits(const u64 *src, const u32 *idx, u64 *out, i64 m) {
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    const i64 padded = (m + 63) & ~63ll;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < padded; j += stride) {
-        bool b = false;
-        if (j < m) {
-            const u32 r = idx[j];
-            b = (src[r >> 6] >> (r & 63)) & 1ull;
-        }
-        const u64 w = __ballot(b);
-        if ((threadIdx.x & 63) == 0) out[j >> 6] = w;
-    }
-}
-void gather_bits(hipStream_t s, const uint64_t *src, const uint32_t *idx, uint64_t *out, int64_t m) {
-    if (m <= 0) return;
-    hipLaunchKernelGGL(k_gather_bits, dim3(grid_for(m)), dim3(256), 0, s, (const u64 *)src, idx, (u64 *)out, (i64)m);
-}
-
 __global__ void __launch_bounds__(256) k_lookup_codes(const int *table, int ntable, const int *codes, int *out, i64 n) {
     const i64 stride = (i64)gridDim.x * blockDim.x;
     for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {

@@ -1,9 +1,11 @@
-// qe_result.cpp -- results: their columns on the device (qe_result_*) and their way to the host, into a caller's pageable
-// buffer (qe_result_column_to_host) or into pinned memory on the copy stream (qe_result_to_host, qe_host_result_*).
+// qe_result.cpp -- results: how the operators build one (new_result, add_column, gather_columns), their columns on the
+// device (qe_result_*) and their way to the host, into a caller's pageable buffer (qe_result_column_to_host) or into pinned
+// memory on the copy stream (qe_result_to_host, qe_host_result_*).
 #include <algorithm>
 #include <thread>
 
 #include "qe_exec.h"
+#include "qe_kernels.h"
 
 namespace qe {
 
@@ -21,6 +23,42 @@ void free_result(qe_ctx *ctx, qe_result *r) {
         ctx->pool.release(c.bytes_valid);
     }
     delete r;
+}
+
+ResultPtr new_result(qe_ctx *ctx, int64_t count) {
+    ResultPtr res = own_result(ctx, new qe_result());
+    res->count = res->capacity = count;
+    return res;
+}
+
+OutColumn &add_column(qe_ctx *ctx, qe_result *res, int type, bool nullable, const std::shared_ptr<DictData> &dict, int64_t nrows) {
+    res->cols.emplace_back();
+    OutColumn &oc = res->cols.back();
+    oc.type = type;
+    oc.nullable = nullable;
+    oc.dict = dict;
+    oc.dict_handle.d = dict;
+    oc.data = ctx->pool.alloc(column_bytes(type, nrows));
+    if (nullable) oc.validity = (uint64_t *)ctx->pool.alloc(bitmap_bytes(nrows));
+    return oc;
+}
+
+void drop_validity(qe_ctx *ctx, OutColumn &c) {
+    ctx->pool.release(c.validity);
+    c.validity = nullptr;
+    c.nullable = false;
+}
+
+void gather_column(qe_ctx *ctx, int type, const void *data, const uint64_t *validity, const uint32_t *rows, int64_t nout, OutColumn &dst,
+                   int max_blocks) {
+    if (type == QE_BOOLEAN) launch_gather_bits_rows(ctx->stream, (const uint64_t *)data, rows, nout, (uint64_t *)dst.data, max_blocks);
+    else launch_gather_rows(ctx->stream, (int)type_width(type), data, rows, nout, dst.data, max_blocks);
+    if (dst.nullable) launch_gather_bits_rows(ctx->stream, validity, rows, nout, dst.validity, max_blocks);
+}
+
+void gather_columns(qe_ctx *ctx, const std::vector<OutColumn> &src_cols, const uint32_t *rows, int64_t nout, qe_result *dst) {
+    for (size_t c = 0; c < src_cols.size(); c++)
+        gather_column(ctx, src_cols[c].type, src_cols[c].data, src_cols[c].validity, rows, nout, dst->cols[c], kGatherBlocks);
 }
 
 }  // namespace qe
@@ -129,8 +167,8 @@ int32_t qe_result_to_host(qe_ctx *ctx, const qe_result *r, qe_host_result **out)
                 hc.dict_handle.d = c.dict;
                 h->cols.push_back(hc);
                 qe_host_result::Col &d = h->cols.back();
-                d.data = ctx->pinned.alloc(std::max<size_t>(column_bytes(c.type, r->count), 64));
-                if (c.validity) d.validity = (uint64_t *)ctx->pinned.alloc(std::max<size_t>(bitmap_bytes(r->count), 64));
+                d.data = ctx->pinned.alloc(column_bytes(c.type, r->count));
+                if (c.validity) d.validity = (uint64_t *)ctx->pinned.alloc(bitmap_bytes(r->count));
             }
             QE_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
             if (r->count > 0) {

@@ -4,7 +4,7 @@
 //
 // Here the source's result already sits in HBM: (1) the key column becomes one u64 per row whose UNSIGNED order is that
 // order (0 = null), (2) the (key, row id) pairs go through a stable LSD radix sort, 4 bits per pass, passes whose digit
-// is the same for every key skipped, (3) every column of the result is gathered through the sorted row ids.  A
+// is the same for every key skipped, (3) every column of the result is gathered through the sorted row ids (qe_kernels.hip).  A
 // different roofline from the scan (16 read-write passes over 12-byte pairs in the worst case), and not part of any
 // BASELINE configuration.
 #include <hip/hip_runtime.h>
@@ -300,34 +300,6 @@ void launch_select_compact(hipStream_t s, const unsigned long long *keys, int64_
     if (n <= 0) return;
     hipLaunchKernelGGL(select_compact_kernel, dim3((unsigned)select_compact_blocks(n)), dim3(256), 0, s, (const u64 *)keys, (i64)n, state, counts, offsets,
                        rows_out, (i64)capacity);
-}
-
-// ---- gather of one bitmap through the sorted row ids (value columns use the per-node gather) ---------------------------
-__global__ void __launch_bounds__(256) gather_bits_rows_kernel(const u64 *src, const u32 *rows, i64 n, u64 *out) {
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    const i64 padded = (n + 63) & ~63ll;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < padded; j += stride) {
-        const bool b = j < n && bit_at(src, (i64)rows[j]);
-        const u64 w = __ballot(b);
-        if ((threadIdx.x & 63) == 0) out[j >> 6] = w;
-    }
-}
-void launch_gather_bits_rows(hipStream_t s, const uint64_t *src, const uint32_t *rows, int64_t n, uint64_t *out) {
-    if (n <= 0) return;
-    const i64 blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(gather_bits_rows_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, s, (const u64 *)src, rows, (i64)n, (u64 *)out);
-}
-
-template <typename T> __global__ void __launch_bounds__(256) gather_rows_kernel(const T *src, const u32 *rows, i64 n, T *out) {
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) out[j] = src[rows[j]];
-}
-void launch_gather_rows(hipStream_t s, int width, const void *src, const uint32_t *rows, int64_t n, void *out) {
-    if (n <= 0) return;
-    const i64 blocks = (n + 255) / 256;
-    const dim3 g((unsigned)(blocks < 8192 ? blocks : 8192));
-    if (width == 8) hipLaunchKernelGGL(gather_rows_kernel<u64>, g, dim3(256), 0, s, (const u64 *)src, rows, (i64)n, (u64 *)out);
-    else hipLaunchKernelGGL(gather_rows_kernel<u32>, g, dim3(256), 0, s, (const u32 *)src, rows, (i64)n, (u32 *)out);
 }
 
 }  // namespace qe

@@ -2,11 +2,9 @@
 // order keys) with the ORDER BY driver, gather every column, mark partition and peer starts, then one segmented scan per
 // function over the gathered columns.
 #include <algorithm>
-#include <functional>
 
 #include "qe_exec.h"
 #include "qe_kernels.h"
-#include "qe_sort_driver.h"
 
 namespace qe {
 namespace {
@@ -16,20 +14,6 @@ constexpr int kMaxWindowKeys = 8, kMaxWindowFns = 16;
 bool is_rank_fn(int fn) { return fn == QE_WIN_ROW_NUMBER || fn == QE_WIN_RANK || fn == QE_WIN_DENSE_RANK; }
 bool is_numeric_agg(int fn) { return fn == QE_WIN_SUM || fn == QE_WIN_MIN || fn == QE_WIN_MAX || fn == QE_WIN_AVG; }
 bool is_shift_fn(int fn) { return fn == QE_WIN_LAG || fn == QE_WIN_LEAD; }
-
-void *alloc_min16(qe_ctx *ctx, size_t bytes) { return ctx->pool.alloc(std::max<size_t>(bytes, 16)); }
-
-OutColumn &add_column(qe_ctx *ctx, qe_result *res, int type, bool nullable, const std::shared_ptr<DictData> &dict, int64_t n) {
-    res->cols.emplace_back();
-    OutColumn &oc = res->cols.back();
-    oc.type = type;
-    oc.nullable = nullable;
-    oc.dict = dict;
-    oc.dict_handle.d = dict;
-    oc.data = alloc_min16(ctx, column_bytes(type, n));
-    if (nullable) oc.validity = (uint64_t *)alloc_min16(ctx, bitmap_bytes(n));
-    return oc;
-}
 
 qe_result *run_window(qe_ctx *ctx, const qe_result *src, const int32_t *part, int32_t npart, const qe_sort_key *order, int32_t norder,
                       const qe_window_fn *fns, int32_t nfn) {
@@ -60,8 +44,7 @@ qe_result *run_window(qe_ctx *ctx, const qe_result *src, const int32_t *part, in
     if (n >= (1ll << 32)) fail(QE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 rows");
     need_device(ctx);
 
-    std::unique_ptr<qe_result, std::function<void(qe_result *)>> res(new qe_result(), [ctx](qe_result *r) { free_result(ctx, r); });
-    res->count = res->capacity = n;
+    ResultPtr res = new_result(ctx, n);
     res->cols.reserve((size_t)(ncols + nfn));
     for (const OutColumn &c : src->cols) add_column(ctx, res.get(), c.type, c.validity != nullptr, c.dict, n);
     for (int32_t f = 0; f < nfn; f++) {
@@ -78,8 +61,8 @@ qe_result *run_window(qe_ctx *ctx, const qe_result *src, const int32_t *part, in
     }
 
     PoolScratch sc(ctx);
-    unsigned long long *pstart = (unsigned long long *)sc.alloc(std::max<size_t>(bitmap_bytes(n), 16));
-    unsigned long long *peer = (unsigned long long *)sc.alloc(std::max<size_t>(bitmap_bytes(n), 16));
+    unsigned long long *pstart = (unsigned long long *)sc.alloc(bitmap_bytes(n));
+    unsigned long long *peer = (unsigned long long *)sc.alloc(bitmap_bytes(n));
     unsigned long long *d_nparts = (unsigned long long *)sc.alloc(16);
     QE_HIP(hipMemsetAsync(d_nparts, 0, 16, ctx->stream));
     unsigned long long h_nparts = 0;
@@ -97,12 +80,10 @@ qe_result *run_window(qe_ctx *ctx, const qe_result *src, const int32_t *part, in
         fa.npartitions = d_nparts;
         if (nkeys > 0) {
             drv.prepare();
-            unsigned long long *kbuf[2] = {(unsigned long long *)ss.alloc((size_t)n * 8), (unsigned long long *)ss.alloc((size_t)n * 8)};
-            uint32_t *rbuf[2] = {(uint32_t *)ss.alloc((size_t)n * 4), (uint32_t *)ss.alloc((size_t)n * 4)};
-            uint32_t *hist = (uint32_t *)ss.alloc((size_t)((n + 1023) / 1024) * 16 * 4);
-            const int cur = drv.sort(n, true, kbuf, rbuf, hist);
-            gather_all_columns(ctx, src, rbuf[cur], n, res.get());
-            fa.perm = rbuf[cur];
+            RadixBuffers rb(ss, n);
+            drv.sort(rb, true);
+            gather_columns(ctx, src->cols, rb.sorted_rows(), n, res.get());
+            fa.perm = rb.sorted_rows();
             for (int32_t k = 0; k < nkeys; k++) {
                 const OutColumn &kc = src->cols[(size_t)keys[(size_t)k].column];
                 fa.type[k] = kc.type;

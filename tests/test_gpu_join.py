@@ -289,6 +289,96 @@ def test_left_join_nulls_every_build_column(gpu_ctx):
         h.free()
 
 
+def test_left_join_without_a_match_at_the_word_boundaries(gpu_ctx):
+    """65 probe rows, every matched one with exactly one partner, rows 0, 63 and 64 without: the "no row" id stands at the
+    first bit of a bitmap word, at its last bit and alone in the next word.  Build columns: a BOOLEAN without validity (all
+    true), a nullable INT32 and a DOUBLE without validity -- its output bitmap comes from a null source bitmap, all ones
+    except under "no row".  Every value beside a "no row" is nonzero / true / valid, so a zero there is the sentinel's."""
+    rng = np.random.default_rng(38)
+    n, nb, none = 65, 80, [0, 63, 64]
+    pkey = rng.integers(0, nb, n).astype(np.int32)
+    pkey[none] = [1000, 1001, 1002]
+    pcols = [Column(I32, pkey), Column(I64, np.arange(n, dtype=np.int64))]
+    ivalid = rng.random(nb) > 0.2
+    ivalid[pkey[[1, 62]]] = True                                                 # the neighbours of the unmatched rows are valid
+    bcols = [Column(I32, np.arange(nb, dtype=np.int32)), Column(B, np.ones(nb, dtype=bool)),
+             Column(I32, rng.integers(1, 1000, nb).astype(np.int32), ivalid), Column(D, rng.integers(1, 50, nb).astype(np.float64))]
+    probe_out, build_out = [1], [1, 2, 3]
+    prow, brow = reference_pairs(pcols, bcols, [0], [0], LEFT)
+    assert prow.tolist() == list(range(n)) and np.nonzero(brow < 0)[0].tolist() == none
+    want = expected_columns(pcols, bcols, prow, brow, probe_out, build_out, LEFT)
+    pside, pfree = as_side(gpu_ctx, pcols, "batch")
+    bside, bfree = as_side(gpu_ctx, bcols, "batch")
+    table = gpu_ctx.join_build(bside, [0])
+    res = table.probe(pside, [0], LEFT, probe_out, build_out)
+    try:
+        assert res.count == n
+        out = res.to_columns()
+        assert_join_output(out, want, brow, len(probe_out), "LEFT, no match at rows 0, 63, 64")
+        assert [bool(res.view(k).nullable) for k in range(res.ncols)] == [False, True, True, True]
+        matched = brow >= 0
+        for k in (1, 2, 3):
+            assert not out[k].valid[none].any() and not out[k].data[none].any()
+        assert out[1].valid[matched].all() and out[1].data[matched].all()         # BOOLEAN: bits of the neighbours untouched
+        assert out[3].valid[matched].all() and (out[3].data[matched] > 0).all()   # DOUBLE: "all ones" from the null bitmap
+        assert np.array_equal(out[2].valid[matched], ivalid[brow[matched]]) and out[2].valid[[1, 62]].all()
+    finally:
+        for h in [res, table] + pfree + bfree:
+            h.free()
+
+
+def test_empty_results_through_every_call_that_makes_one(gpu_ctx):
+    """Zero rows through every call that builds a result: a concatenation of empty parts, ORDER BY with and without LIMIT, an
+    INNER join whose probe side matches nothing, a LEFT join of no probe rows, the window operator and a hashed GROUP BY
+    whose filter keeps no row.  Each gives the right column types and count 0, can be read and can be freed -- every
+    buffer of such a result is a zero-byte request to the device pool."""
+    ctx = gpu_ctx
+    rng = np.random.default_rng(39)
+    n = 100
+    cols = [Column(I32, rng.integers(0, 10, n).astype(np.int32)), Column(D, rng.normal(0, 1, n), rng.random(n) > 0.2),
+            Column(B, rng.random(n) > 0.5, rng.random(n) > 0.2), Column(S, rng.integers(0, len(TAGS), n).astype(np.int32), None, TAGS),
+            Column(I64, np.arange(n, dtype=np.int64))]
+    types = [c.type for c in cols]
+    batch = E.DeviceBatch.from_columns(ctx, cols)
+    ident = [ctx.compile(ColumnExpression(f"c{i}", i, c.type)) for i, c in enumerate(cols)]
+    nothing = ctx.compile(fn(Fn.CMP_LT, col("id", 4, I64), num(-1.0)))
+    full = E.filter_project(ctx, batch, None, ident)
+    empty = E.filter_project(ctx, batch, nothing, ident)
+    made = [full, empty]
+
+    def check(res, want_types, what):
+        made.append(res)
+        assert res.count == 0 and res.ncols == len(want_types), what
+        out = res.to_columns()
+        assert [c.type for c in out] == want_types and all(len(c) == 0 for c in out), what
+        for k, t in enumerate(want_types):
+            assert res.view(k).type == int(t), what
+            if t == S:
+                assert out[k].dictionary == TAGS, what
+
+    try:
+        assert full.count == n and empty.count == 0
+        check(ctx.concat([empty, empty, empty]), types, "concat of empty parts")
+        check(ctx.order_by_keys(empty, [(0, False), (1, True)]), types, "ORDER BY over no rows")
+        check(ctx.order_by_keys(empty, [(1, True)], limit=3), types, "ORDER BY .. LIMIT over no rows")
+        check(ctx.order_by_keys(full, [(1, True)], limit=0), types, "ORDER BY .. LIMIT 0")
+        table = ctx.join_build(full, [0])                                       # keys 0 .. 9
+        made.append(table)
+        other = E.DeviceBatch.from_columns(ctx, [Column(I32, np.arange(100, 150, dtype=np.int32)), Column(D, rng.normal(0, 1, 50))])
+        made.append(other)
+        check(table.probe(other, [0], INNER, [0, 1], [1, 2, 3, 4]), [I32, D, D, B, S, I64], "INNER join without a match")
+        assert ctx.last_join_stats()[:3] == [n, 50, 0]
+        check(table.probe(empty, [0], LEFT, [0, 4], [1, 2, 3]), [I32, I64, D, B, S], "LEFT join of no probe rows")
+        check(ctx.window(empty, [0], [(4, False)], [(N.WIN_ROW_NUMBER, 0, 0), (N.WIN_SUM, 1, 0), (N.WIN_LAG, 3, 1)]),
+              types + [I64, D, S], "window over no rows")
+        keys, exprs = [ctx.compile(col("v", 1, D))], [ctx.compile(col("v", 1, D)), ctx.compile(col("v", 1, D))]
+        check(E.filter_groupby(ctx, batch, nothing, keys, exprs, [int(AF.SUM), int(AF.COUNT)]), [D, D, D], "hashed GROUP BY, no row kept")
+        assert ctx.last_form == N.FORM_GROUPBY_HASHED
+    finally:
+        for h in made[::-1] + [batch]:
+            h.free()
+
+
 def test_the_same_bytes_on_every_run_and_context(gpu_ctx):
     rng = np.random.default_rng(37)
     np_, nb = 8_009, 2_003

@@ -23,7 +23,7 @@ TAGS = ["t0", "", "täg", "t3", "t4"]
 PROBE_BLOCK = 256                # rows per block of join_count_kernel / join_write_kernel
 SCAN_WIDTH = 1024                # block sums per trip of join_scan_kernel
 ROW_GRID = 8192 * 256            # threads of the capped grids of join_build_keys_kernel, join_directory_kernel, gather_rows_kernel
-GATHER_GRID = 16384 * 256        # ... of join_gather_kernel and join_gather_bits_kernel
+GATHER_GRID = 16384 * 256        # ... of gather_rows_kernel and gather_bits_rows_kernel as the join launches them for its output columns
 RADIX_SCAN_WIDTH = 1024          # counters per trip of radix_scan_kernel: 16 per 1024 rows
 
 
@@ -197,8 +197,8 @@ def test_build_side_past_the_grid_cap(gpu_ctx, null_share):
 # ---- d. an output larger than the gathers' capped grid --------------------------------------------------------------------
 @pytest.mark.parametrize("jt", [LEFT, INNER], ids=lambda j: JOIN_NAMES[j])
 def test_output_past_the_gather_cap(gpu_ctx, jt):
-    """300 000 probe rows x 16 matches: more than 16384 x 256 output rows, so join_gather_kernel (4 and 8 bytes) and
-    join_gather_bits_kernel (BOOLEAN values, validity) stride.  The INNER result then enters one more plan as a batch."""
+    """300 000 probe rows x 16 matches: more than 16384 x 256 output rows, so gather_rows_kernel (4 and 8 bytes) and
+    gather_bits_rows_kernel (BOOLEAN values, validity) stride.  The INNER result then enters one more plan as a batch."""
     ctx = gpu_ctx
     rng = np.random.default_rng(64)
     nkeys, n = 200, 300_000
