@@ -413,8 +413,8 @@ int32_t qe_ctx_last_join_stats(const qe_ctx *ctx, int64_t out[4]);
  *
  * Columns: all input columns first, types, nullability and dictionaries unchanged; then one column per entry of `fns`.
  *
- * Frame: always ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW within the partition.  It counts rows, so peers are not
- * pulled in; whole-partition totals remain group-by + join.
+ * Frame: qe_result_window always uses ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW within the partition.  It counts rows,
+ * so peers are not pulled in.  Sliding and whole-partition frames: qe_result_window_frames below.
  *
  * Functions:
  *   ROW_NUMBER (1-based), RANK (row number of the first peer), DENSE_RANK: INT64, not nullable; `column` is ignored.
@@ -450,7 +450,47 @@ int32_t qe_result_window(qe_ctx *ctx, const qe_result *result,
                          const int32_t *partition_cols, int32_t npart,
                          const qe_sort_key *order, int32_t norder,
                          const qe_window_fn *fns, int32_t nfn, qe_result **out);
-/* what the last qe_result_window of this context did: out[0] rows, out[1] partitions, out[2] scan tiles (2048 rows each),
+/* ---- window frames --------------------------------------------------------------------------------------------------------
+ * qe_result_window with a frame per function: ROWS BETWEEN `preceding` PRECEDING AND `following` FOLLOWING, each either
+ * QE_FRAME_UNBOUNDED or a row count in [0, 2^31).  With the partition of row j being rows [start, end] of the sorted order,
+ * the frame of row j is [lo, hi]:
+ *     lo = start if preceding == QE_FRAME_UNBOUNDED, else max(start, j - preceding)
+ *     hi = end   if following == QE_FRAME_UNBOUNDED, else min(end,   j + following)
+ * so it always holds the current row and is never empty; it counts rows (ROWS mode): peers are not pulled in.  A moving
+ * average is (p, f); a whole-partition value on every row is (UNBOUNDED, UNBOUNDED); (UNBOUNDED, 0) is the running frame,
+ * and every function of qe_result_window given that frame here returns the bytes qe_result_window returns (qe_result_window
+ * IS this call with that frame).  Rows, order, input columns, limits and errors are those of qe_result_window.
+ *
+ * Functions that read the frame:
+ *   SUM, COUNT, MIN, MAX, AVG over the frame's rows: NULL handling, special values, the conversion to double and the output
+ *     types are those of qe_result_window (DOUBLE; COUNT not nullable, the others NULL while the frame holds no valid value).
+ *     A special value counts only while it is inside the frame: the rows after an Inf or a NaN has left are finite again.
+ *   FIRST_VALUE, LAST_VALUE over a column of any type: value and validity of row lo / row hi; a NULL there is returned as
+ *     NULL (no IGNORE NULLS); the output has the source column's type, nullability and dictionary.
+ * Functions that ignore the frame: the three ranks and LAG / LEAD; preceding and following must both be 0 for them.
+ *
+ * How: a frame's value is only ever built from values of rows inside the frame, never as a difference of two running sums.
+ * With W = preceding + following + 1, a forward scan P restarted at partition starts and at every row j with j % W == 0 and a
+ * reverse scan S restarted at partition ends and after every row with j % W == W - 1 are kept; the frame touches at most two
+ * adjacent blocks of W rows and its value is P[hi], S[lo] or combine(S[lo], P[hi]).  One-sided frames read one plain scan
+ * (forward at hi, or reverse at lo).  The scans have the fixed shape described above, so the determinism statement holds for
+ * frames: the same inputs give the same bytes on every run and every context, no look-back, no atomic feeds a result byte.
+ *
+ * Numerics: a framed SUM is within gamma_c * sum|x| of the exact sum of the frame's valid values, c = valid values IN THE FRAME
+ * and sum|x| over the frame (not the prefix); AVG: gamma_(c+1) * sum|x| / c; integer-valued data below 2^53 comes out exact.
+ *
+ * Errors beyond those of qe_result_window (QE_ERR_INVALID_ARG, *out = NULL): preceding or following below -1 or >= 2^31; a
+ * non-zero preceding or following on a rank or on LAG / LEAD; FIRST_VALUE / LAST_VALUE with a column out of range.
+ * qe_ctx_last_window_stats reports this call too. */
+#define QE_FRAME_UNBOUNDED (-1)
+enum { QE_WIN_FIRST_VALUE = 10, QE_WIN_LAST_VALUE = 11 };   /* continue QE_WIN_*; known to qe_result_window_frames only */
+typedef struct { int32_t fn; int32_t column; int64_t offset;   /* as qe_window_fn */
+                 int64_t preceding; int64_t following; } qe_window_frame_fn;
+int32_t qe_result_window_frames(qe_ctx *ctx, const qe_result *result,
+                                const int32_t *partition_cols, int32_t npart,
+                                const qe_sort_key *order, int32_t norder,
+                                const qe_window_frame_fn *fns, int32_t nfn, qe_result **out);
+/* what the last qe_result_window / qe_result_window_frames of this context did: out[0] rows, out[1] partitions, out[2] scan tiles (2048 rows each),
  * out[3] trips of the tile-aggregate scan (1024 tiles each) */
 int32_t qe_ctx_last_window_stats(const qe_ctx *ctx, int64_t out[4]);
 

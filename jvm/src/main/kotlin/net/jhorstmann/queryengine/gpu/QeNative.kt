@@ -69,6 +69,9 @@ internal object QeNative {
     // long offset}, nfn (1..16), qe_result** -> status: every input column sorted by (partition, order), then one column per function
     // (fn: 0 ROW_NUMBER, 1 RANK, 2 DENSE_RANK, 3 SUM, 4 COUNT, 5 MIN, 6 MAX, 7 AVG, 8 LAG, 9 LEAD)
     val qe_result_window = handle("qe_result_window", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS)
+    // the same with a frame per function: qe_window_frame_fn fns[nfn] {int fn, int column, long offset, long preceding, long following}
+    // (ROWS BETWEEN preceding PRECEDING AND following FOLLOWING, -1 = UNBOUNDED; fn 10 / 11 = FIRST_VALUE / LAST_VALUE), qe_result **out
+    val qe_result_window_frames = handle("qe_result_window_frames", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS)
     val qe_ctx_last_window_stats = handle("qe_ctx_last_window_stats", JAVA_INT, ADDRESS, ADDRESS)     // ctx, long[4]
     // ctx, result, qe_batch** -> status: a batch whose columns ARE the result's (zero copy): the input of the next plan
     val qe_batch_from_result = handle("qe_batch_from_result", JAVA_INT, ADDRESS, ADDRESS, ADDRESS)

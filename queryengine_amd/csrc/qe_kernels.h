@@ -159,29 +159,51 @@ struct WinFlagArgs {
 };
 void launch_win_flags(hipStream_t s, const WinFlagArgs &a);
 // One segmented inclusive scan over the n rows, restarted at every set bit of pstart, in three fixed-shape steps: per-tile
-// reduce, one workgroup over the tile aggregates (kWinTripTiles per trip), per-tile downsweep.
+// reduce, one workgroup over the tile aggregates (kWinTripTiles per trip), per-tile downsweep.  reverse: the scan runs from
+// row n - 1 down and restarts after every row that ENDS a partition (the next row's pstart bit, or row n - 1); block > 0: it
+// also restarts at every row j with j % block == 0 (reverse: after every row with j % block == block - 1).
 enum { QE_WSCAN_SUM = 0, QE_WSCAN_MIN = 1, QE_WSCAN_MAX = 2, QE_WSCAN_INDEX = 3 };
-enum { QE_WOUT_SUM = 0, QE_WOUT_MINMAX = 1, QE_WOUT_AVG = 2, QE_WOUT_COUNT = 3, QE_WOUT_COUNT_I64 = 4, QE_WOUT_INDEX = 5 };
+enum { QE_WOUT_SUM = 0, QE_WOUT_MINMAX = 1, QE_WOUT_AVG = 2, QE_WOUT_COUNT = 3, QE_WOUT_COUNT_I64 = 4, QE_WOUT_INDEX = 5, QE_WOUT_ITEM = 6 };
 struct WinScanArgs {
     int op;                                 // QE_WSCAN_*
     int out_mode;                           // QE_WOUT_*
     int type;                               // QE_DOUBLE / QE_INT64 / QE_INT32 of data
     const void *data;                       // null: only the count of valid rows is scanned
     const unsigned long long *validity;     // null: every row valid.  QE_WSCAN_INDEX: the bitmap whose last set bit at or before each row is wanted
+                                            // (reverse: a partition-start bitmap; the first partition END at or after each row is wanted)
     const unsigned long long *pstart;       // null: one segment
+    int reverse;                            // 1: from row n - 1 down
+    long long block;                        // > 0 (and < 2^32): extra restarts at the edges of blocks of this many rows
     long long n, ntiles;
     double *tile_v, *carry_v;               // ntiles each: the tile aggregates, and what the scan over them carries into each tile
     unsigned int *tile_c, *tile_f, *carry_c;
-    void *out;                              // f64 (SUM, MINMAX, AVG, COUNT), i64 (COUNT_I64) or u32 (INDEX) per row
+    void *out;                              // f64 (SUM, MINMAX, AVG, COUNT, ITEM), i64 (COUNT_I64) or u32 (INDEX) per row
+    unsigned int *out_c;                    // QE_WOUT_ITEM: the scanned pair {out[j], out_c[j]} = {value, valid values} as it stands
     unsigned long long *out_valid;          // SUM, MINMAX, AVG: bit j = a valid value has been seen in the partition up to row j
 };
 void launch_win_scan(hipStream_t s, const WinScanArgs &a);
 // out[j] = (first ? first[j] : j) - start[j] + 1: ROW_NUMBER (first null) and RANK (first = index of the first peer)
 void launch_win_rank(hipStream_t s, const uint32_t *start, const uint32_t *first, int64_t n, int64_t *out);
-// LAG / LEAD: out[j] = src[j + delta] where that row exists and start[j + delta] == start[j], else zero with validity 0;
-// width 8 / 4, or 0 for a bitmap column; src_valid null = every source row valid
-void launch_win_shift(hipStream_t s, int width, const void *src, const uint64_t *src_valid, const uint32_t *start, int64_t n,
-                      int64_t delta, void *out, uint64_t *out_valid);
+// A framed aggregate, one elementwise pass: the frame of row j is [lo, hi] = [preceding < 0 ? start[j] : max(start[j], j -
+// preceding), following < 0 ? end[j] : min(end[j], j + following)].  preceding < 0: the value is P[hi] of a plain forward
+// scan; else following < 0: S[lo] of a plain reverse scan; else P / S are the forward / reverse scans with block = preceding +
+// following + 1 and the value is P[hi], S[lo] or combine(S[lo], P[hi]).  Written through out_mode like a scan's result.
+struct WinFrameArgs {
+    int op;                                 // QE_WSCAN_SUM / MIN / MAX
+    int out_mode;                           // QE_WOUT_SUM / MINMAX / AVG / COUNT
+    long long n, preceding, following;
+    const unsigned int *start, *end;        // first and last row of every row's partition
+    const double *p_v, *s_v;                // the scanned pairs (QE_WOUT_ITEM); the pair that is not read may be null
+    const unsigned int *p_c, *s_c;
+    void *out;
+    unsigned long long *out_valid;          // null for COUNT
+};
+void launch_win_frame(hipStream_t s, const WinFrameArgs &a);
+// LAG / LEAD (end null): out[j] = src[j + delta] where that row exists and start[j + delta] == start[j], else zero with
+// validity 0.  FIRST_VALUE / LAST_VALUE (end given): out[j] = src[min(max(j + delta, start[j]), end[j])] with that row's validity.
+// width 8 / 4, or 0 for a bitmap column; src_valid null = every source row valid; out_valid null = no validity is written
+void launch_win_shift(hipStream_t s, int width, const void *src, const uint64_t *src_valid, const uint32_t *start, const uint32_t *end,
+                      int64_t n, int64_t delta, void *out, uint64_t *out_valid);
 
 // ---- gathers through u32 row ids (qe_kernels.hip): ORDER BY, window, join, per-node ----
 // grid caps, in blocks of 256 threads: every caller's, and the join's output columns (with the narrow cap the probe was 0.4 to

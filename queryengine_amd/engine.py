@@ -20,6 +20,18 @@ from .table import Column, pack_bitmap, unpack_bitmap
 _NP = {DataType.DOUBLE: np.float64, DataType.INT64: np.int64, DataType.INT32: np.int32, DataType.STRING: np.int32}
 
 
+def window_frame_fn(f: Sequence) -> tuple:
+    """(fn, column, offset, preceding, following) of one window function entry: up to three elements mean the running frame
+    (UNBOUNDED PRECEDING .. CURRENT ROW) for the aggregates and no frame (0, 0) for the ranks and LAG / LEAD; longer entries
+    are padded with zeros."""
+    f = tuple(int(v) for v in f)
+    if len(f) <= 3:
+        fn = f[0] if f else -1
+        running = N.WIN_SUM <= fn <= N.WIN_AVG
+        return (f + (0, 0, 0))[:3] + ((N.FRAME_UNBOUNDED, 0) if running else (0, 0))
+    return (f + (0,))[:5]
+
+
 class Context:
     """qe_ctx: one device + one HIP stream.  ``device=None`` -> planning-only (QE_DEVICE_NONE)."""
 
@@ -178,17 +190,27 @@ class Context:
         return [int(v) for v in out]
 
     def window(self, result: "Result", partition_by: Sequence[int], order_by: Sequence, functions: Sequence) -> "Result":
-        """qe_result_window: every row of `result`, sorted stably by `partition_by` (columns, ascending) and then by `order_by`
-        = [(column, descending), ...], followed by one column per entry of `functions` = [(native.WIN_*, column, offset), ...]
-        (column: the argument, ignored by the ranks; offset: LAG / LEAD only; shorter tuples are padded with zeros).  The frame
-        is ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW inside the partition."""
+        """qe_result_window / qe_result_window_frames: every row of `result`, sorted stably by `partition_by` (columns,
+        ascending) and then by `order_by` = [(column, descending), ...], followed by one column per entry of `functions` =
+        [(native.WIN_*, column, offset[, preceding, following]), ...] (column: the argument, ignored by the ranks; offset: LAG /
+        LEAD only; shorter tuples are padded with zeros).  Entries of three elements or fewer have the frame ROWS BETWEEN
+        UNBOUNDED PRECEDING AND CURRENT ROW, and a list of only such entries is one qe_result_window.  A longer entry names its
+        frame, ROWS BETWEEN preceding PRECEDING AND following FOLLOWING, each native.FRAME_UNBOUNDED or a row count (both 0 for
+        the ranks and LAG / LEAD); then the whole list goes through qe_result_window_frames."""
         order_by = list(order_by)
-        fns = [(tuple(f) + (0, 0))[:3] for f in functions]
+        functions = [tuple(f) for f in functions]
         keys = (N.SortKey * max(1, len(order_by)))(*[N.SortKey(int(c), 1 if d else 0) for c, d in order_by])
-        arr = (N.WindowFn * max(1, len(fns)))(*[N.WindowFn(int(f), int(c), int(o)) for f, c, o in fns])
         h = C.c_void_p()
-        N.check(self.handle, self._lib.qe_result_window(self.handle, result.handle, _i32_array(partition_by), len(partition_by),
-                                                        keys, len(order_by), arr, len(fns), C.byref(h)))
+        if all(len(f) <= 3 for f in functions):
+            fns = [(f + (0, 0))[:3] for f in functions]
+            arr = (N.WindowFn * max(1, len(fns)))(*[N.WindowFn(int(f), int(c), int(o)) for f, c, o in fns])
+            call = self._lib.qe_result_window
+        else:
+            fns = [window_frame_fn(f) for f in functions]
+            arr = (N.WindowFrameFn * len(fns))(*[N.WindowFrameFn(*f) for f in fns])
+            call = self._lib.qe_result_window_frames
+        N.check(self.handle, call(self.handle, result.handle, _i32_array(partition_by), len(partition_by), keys, len(order_by), arr, len(fns),
+                                  C.byref(h)))
         return Result(self, h)
 
     def last_window_stats(self) -> dict:

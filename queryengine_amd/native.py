@@ -31,6 +31,8 @@ FORM_RING, FORM_TWO_PASS, FORM_DENSE, FORM_PER_NODE, FORM_NO_FILTER, FORM_LOCAL 
 FORM_GROUPBY_DENSE, FORM_GROUPBY_HASHED, FORM_GROUPBY_HASH_PARTITIONED = 8, 9, 10
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = range(4)
 WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_SUM, WIN_COUNT, WIN_MIN, WIN_MAX, WIN_AVG, WIN_LAG, WIN_LEAD = range(10)
+WIN_FIRST_VALUE, WIN_LAST_VALUE = 10, 11        # qe_result_window_frames only
+FRAME_UNBOUNDED = -1                             # QE_FRAME_UNBOUNDED: a frame edge at the partition's edge
 WIN_TILE_ROWS, WIN_TRIP_TILES = 2048, 1024   # the scan's tile and the tile aggregates one trip covers
 
 
@@ -79,6 +81,12 @@ class JoinInput(C.Structure):
 class WindowFn(C.Structure):
     """qe_window_fn: one window function (column: its argument, ignored by the ranks; offset: LAG / LEAD only)."""
     _fields_ = [("fn", C.c_int32), ("column", C.c_int32), ("offset", C.c_int64)]
+
+
+class WindowFrameFn(C.Structure):
+    """qe_window_frame_fn: a window function with its frame, ROWS BETWEEN preceding PRECEDING AND following FOLLOWING
+    (each FRAME_UNBOUNDED or a row count; both 0 for the ranks and LAG / LEAD, which ignore the frame)."""
+    _fields_ = [("fn", C.c_int32), ("column", C.c_int32), ("offset", C.c_int64), ("preceding", C.c_int64), ("following", C.c_int64)]
 
 
 # every symbol include/qe_hip.h declares: (name, restype, argtypes)
@@ -152,6 +160,7 @@ SYMBOLS = [
                                   C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_P)]),
     ("qe_ctx_last_join_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_result_window", C.c_int32, [_P, _P, C.POINTER(C.c_int32), C.c_int32, _P, C.c_int32, C.POINTER(WindowFn), C.c_int32, C.POINTER(_P)]),
+    ("qe_result_window_frames", C.c_int32, [_P, _P, C.POINTER(C.c_int32), C.c_int32, _P, C.c_int32, C.POINTER(WindowFrameFn), C.c_int32, C.POINTER(_P)]),
     ("qe_ctx_last_window_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_batch_from_result", C.c_int32, [_P, _P, C.POINTER(_P)]),
     ("qe_comm_unique_id", C.c_int32, [_P, _P]),

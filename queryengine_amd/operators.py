@@ -281,35 +281,48 @@ def _window_min(a: float, b: float, want_max: bool) -> float:
 class WindowOperator(Operator):
     """Window functions over a source: every source row, sorted stably by ``partition_by`` (column indices, ascending) and
     then by ``order_by`` (``[(column, descending), ...]``, the comparator of ``OrderByOperator``), followed by one value
-    per entry of ``functions`` = ``[(fn, column, offset), ...]`` (``fn`` one of ``native.WIN_*``; ``column`` is ignored by the
-    three ranks, ``offset`` is read by LAG / LEAD only; shorter tuples are padded with zeros).
+    per entry of ``functions`` = ``[(fn, column, offset), ...]`` or ``[(fn, column, offset, preceding, following), ...]``
+    (``fn`` one of ``native.WIN_*``; ``column`` is ignored by the three ranks, ``offset`` is read by LAG / LEAD only; shorter
+    tuples are padded with zeros).
 
     Adjacent rows share a partition when they compare equal on every partition column (``None`` is a key value, all NaNs
     are one value, -0.0 and 0.0 are two); peers are rows of a partition that compare equal on every order key.  The frame
-    is always ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW.  ROW_NUMBER, RANK (the row number of the first peer) and
+    of an entry of three elements or fewer is ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW.  A longer entry names its
+    frame: ROWS BETWEEN ``preceding`` PRECEDING AND ``following`` FOLLOWING, each ``native.FRAME_UNBOUNDED`` or a row count
+    in [0, 2^31), clamped to the partition -- rows ``max(start, i - preceding) .. min(end, i + following)``, which always
+    hold the current row; SUM / COUNT / MIN / MAX / AVG read those rows, FIRST_VALUE / LAST_VALUE (these need a long entry)
+    give the value of the first / last of them, ``None`` included; the ranks and LAG / LEAD take no frame (both must be
+    0).  ROW_NUMBER, RANK (the row number of the first peer) and
     DENSE_RANK are ints; SUM / MIN / MAX / AVG skip ``None`` and are ``None`` until the partition has shown a value; COUNT
     counts the values so far (an int, like the COUNT of the aggregation operators); LAG / LEAD give the value ``offset``
     rows before / after in the partition, ``None`` beyond its edge.  The reference has no windows (Query.g4).
 
-    When the source is a GPU operator (``result()`` and ``ctx``) the rows never leave HBM (qe_result_window) and the
+    When the source is a GPU operator (``result()`` and ``ctx``) the rows never leave HBM (qe_result_window, or
+    qe_result_window_frames as soon as one entry names a frame) and the
     operator offers ``result()`` and ``ctx`` itself.  Any other source is drained and evaluated on the host: stable sorts
-    with ``_compare_key``, then one sequential loop per partition -- the executable statement of the semantics, and the
-    expectation of the device tests."""
+    with ``_compare_key``, then one sequential loop per partition (per row over the rows of its frame, when a frame is
+    named) -- the executable statement of the semantics, and the expectation of the device tests."""
 
     def __init__(self, source: Operator, partition_by: Sequence[int], order_by: Sequence, functions: Sequence):
         self.source = source
         self.partition_by = [int(c) for c in partition_by]
         self.order_by = [(int(c), bool(d)) for c, d in order_by]
-        self.functions = [tuple(int(v) for v in (tuple(f) + (0, 0))[:3]) for f in functions]
+        # short entries stay 3-tuples (the running frame, qe_result_window); an entry that names a frame is a 5-tuple
+        self.functions = [tuple(int(v) for v in ((tuple(f) + (0, 0))[:3] if len(tuple(f)) <= 3 else (tuple(f) + (0,))[:5])) for f in functions]
+        self._frames = [E.window_frame_fn(f) for f in self.functions]
         if len(self.partition_by) + len(self.order_by) > 8:
             raise ValueError("WindowOperator: at most 8 partition and order columns")
         if not 1 <= len(self.functions) <= 16:
             raise ValueError("WindowOperator: 1 to 16 functions")
-        for fn, _, offset in self.functions:
-            if not N.WIN_ROW_NUMBER <= fn <= N.WIN_LEAD:
+        for given, (fn, _, offset, preceding, following) in zip(self.functions, self._frames):
+            if not N.WIN_ROW_NUMBER <= fn <= (N.WIN_LEAD if len(given) == 3 else N.WIN_LAST_VALUE):
                 raise ValueError("WindowOperator: unknown window function")
             if fn in (N.WIN_LAG, N.WIN_LEAD) and not 0 <= offset < 2 ** 31:
                 raise ValueError("WindowOperator: 0 <= offset < 2^31")
+            if not (-1 <= preceding < 2 ** 31 and -1 <= following < 2 ** 31):
+                raise ValueError("WindowOperator: preceding and following are FRAME_UNBOUNDED or in [0, 2^31)")
+            if not N.WIN_SUM <= fn <= N.WIN_AVG and fn not in (N.WIN_FIRST_VALUE, N.WIN_LAST_VALUE) and (preceding, following) != (0, 0):
+                raise ValueError("WindowOperator: the ranks and LAG / LEAD take no frame")
         self._on_device = hasattr(source, "result") and hasattr(source, "ctx")
         if self._on_device:
             self.ctx = source.ctx
@@ -321,8 +334,8 @@ class WindowOperator(Operator):
         first = len(cols) - len(self.functions)
         for i in range(len(cols[0]) if cols else 0):
             row = [c.value(i) for c in cols]
-            for k, (fn, _, _) in enumerate(self.functions):
-                if fn == N.WIN_COUNT:
+            for k, f in enumerate(self.functions):
+                if f[0] == N.WIN_COUNT:
                     row[first + k] = int(row[first + k])
             yield row
 
@@ -330,7 +343,7 @@ class WindowOperator(Operator):
         data = mapTo(self.source, [], lambda row: list(row))
         for column, descending in reversed([(c, False) for c in self.partition_by] + self.order_by):
             data.sort(key=lambda row: _compare_key(row[column]), reverse=descending)
-        for fn, column, _ in self.functions:
+        for fn, column, *_ in self.functions:
             if fn in (N.WIN_SUM, N.WIN_MIN, N.WIN_MAX, N.WIN_AVG):
                 for row in data:
                     if isinstance(row[column], (bool, str)):
@@ -346,7 +359,10 @@ class WindowOperator(Operator):
                 end += 1
             part = data[begin:end]
             values = [[] for _ in self.functions]
-            for k, (fn, column, offset) in enumerate(self.functions):
+            for k, (fn, column, offset, preceding, following) in enumerate(self._frames):
+                if fn in (N.WIN_FIRST_VALUE, N.WIN_LAST_VALUE) or (N.WIN_SUM <= fn <= N.WIN_AVG and (preceding, following) != (N.FRAME_UNBOUNDED, 0)):
+                    values[k] = [self._framed(part, i, fn, column, preceding, following) for i in range(len(part))]
+                    continue
                 rank = dense = 0
                 total, count, extreme = 0.0, 0, None      # Accumulators.kt:40: a sum starts from 0.0
                 for i, row in enumerate(part):
@@ -383,6 +399,31 @@ class WindowOperator(Operator):
             out.extend(row + [values[k][i] for k in range(len(self.functions))] for i, row in enumerate(part))
             begin = end
         return out
+
+    @staticmethod
+    def _framed(part, i, fn, column, preceding, following):
+        """One function over the frame of row i of a partition: the rows lo .. hi, one after the other."""
+        lo = 0 if preceding == N.FRAME_UNBOUNDED else max(0, i - preceding)
+        hi = len(part) - 1 if following == N.FRAME_UNBOUNDED else min(len(part) - 1, i + following)
+        if fn == N.WIN_FIRST_VALUE:
+            return part[lo][column]
+        if fn == N.WIN_LAST_VALUE:
+            return part[hi][column]
+        total, count, extreme = 0.0, 0, None      # Accumulators.kt:40: a sum starts from 0.0
+        for row in part[lo:hi + 1]:
+            v = row[column]
+            if v is None:
+                continue
+            count += 1
+            if fn in (N.WIN_SUM, N.WIN_AVG):
+                total += float(v)
+            elif fn in (N.WIN_MIN, N.WIN_MAX):
+                extreme = float(v) if extreme is None else _window_min(extreme, float(v), fn == N.WIN_MAX)
+        if fn == N.WIN_COUNT:
+            return count
+        if count == 0:
+            return None
+        return total if fn == N.WIN_SUM else total / count if fn == N.WIN_AVG else extreme
 
     def open(self) -> None:
         if self._on_device:
