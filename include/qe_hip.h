@@ -494,6 +494,61 @@ int32_t qe_result_window_frames(qe_ctx *ctx, const qe_result *result,
  * out[3] trips of the tile-aggregate scan (1024 tiles each) */
 int32_t qe_ctx_last_window_stats(const qe_ctx *ctx, int64_t out[4]);
 
+/* ---- ordered-set aggregates per group ------------------------------------------------------------------------
+ * The aggregates that cannot be merged from partials -- a median or percentile, COUNT(DISTINCT x), the most frequent value --
+ * per group, over a result, without copying sorted rows to the host.  The reference has none of them (Query.g4).  With no
+ * function the call is SELECT DISTINCT over the group columns.
+ *
+ * Rows and order: one row per group, the groups ASCENDING by the group columns under the comparator of
+ * qe_result_order_by_keys (NULL first, Double.compareTo, strings by compareTo, false < true).  This is NOT the insertion order
+ * of qe_filter_groupby.  Two rows share a group exactly when two window rows share a partition: NULL is a key value, every NaN
+ * is one value, -0.0 != 0.0, STRING compares by string.  ngroup == 0: the whole input is one group.
+ *
+ * Columns: the ngroup group columns first (type, dictionary and nullability of the source column), then one column per entry
+ * of `fns`.  nfn == 0 is allowed when ngroup >= 1 and returns the distinct key tuples.
+ * Limits: 0 <= ngroup <= 7 (group columns plus one argument are the sort's 8 keys), 0 <= nfn <= 16, ngroup + nfn >= 1.
+ *
+ * Functions.  The values of a group for column x are its non-NULL values v[0 .. c-1], ascending under the sort comparator
+ * (Double.compareTo: -0.0 < 0.0, NaN greatest; false < true; strings by compareTo).
+ *   COUNT_DISTINCT   any type.  The number of distinct v under the engine's `=`: all NaNs are one value, -0.0 and 0.0 are two.
+ *                    DOUBLE, not nullable, like every COUNT here; 0 for a group without a valid value.
+ *   PERCENTILE_DISC  any type, BOOLEAN and STRING included.  v[k], k = max(ceil(fraction * (double)c) - 1, 0), the product one
+ *                    IEEE f64 multiplication.  Source type and dictionary, always nullable, NULL when c == 0.
+ *   PERCENTILE_CONT  DOUBLE, INT64 or INT32.  The values are converted to double, as the group-by aggregates convert them,
+ *                    AFTER sorting in the column's own order.  With h = fraction * (double)(c - 1), lo = floor(h), hi = ceil(h),
+ *                    frac = h - lo: the value is v[lo] when frac == 0 or v[lo] and v[hi] have the same bits (as doubles), else
+ *                    v[lo] + (v[hi] - v[lo]) * frac, evaluated in exactly this order without FMA contraction:
+ *                    the result is defined to the bit.  The median of two equal infinities is that infinity; -Inf against
+ *                    +Inf, or a NaN in reach, gives what the formula gives.  DOUBLE, always nullable, NULL when c == 0.
+ *                    MEDIAN is PERCENTILE_CONT with fraction 0.5.
+ *   MODE             any type.  The value of the longest run of equal values (equal under `=`); of several longest runs the
+ *                    smallest value.  Source type and dictionary, always nullable, NULL when c == 0.
+ * `fraction` is read by the two percentiles only.  A NULL output has validity 0 and value zero.
+ *
+ * Zero input rows: with ngroup >= 1 a zero-row result with the full schema; with ngroup == 0 one row, COUNT_DISTINCT 0 and
+ * every other function NULL (Accumulators.kt: empty => null, as in qe_filter_aggregate).
+ *
+ * How: one stable sort by (group columns, argument) per DISTINCT argument column -- functions that share an argument share
+ * the sort -- then the boundary flags of the window operator, ranks and compaction of those bitmaps, and one small pass per
+ * function; columns that hold source values are gathered from the source through a per-group row list.
+ *
+ * Determinism: the same inputs give the same bytes on every run and every context.  No floating-point value is combined by an
+ * atomic; the only atomics are an integer add (the group count) and an integer max (MODE), whose results do not depend on the
+ * order of arrival.
+ *
+ * Errors (*out = NULL): QE_ERR_INVALID_ARG for a null pointer, ngroup or nfn out of range or both zero, a column out of range,
+ * an unknown fn, PERCENTILE_CONT over BOOLEAN or STRING, a percentile fraction that is NaN or outside [0, 1], a STRING group or
+ * argument column without a dictionary; QE_ERR_UNSUPPORTED for 2^32 rows or more; QE_ERR_HIP on a planning-only context;
+ * QE_ERR_OOM when scratch or output does not fit. */
+enum { QE_OSA_COUNT_DISTINCT = 0, QE_OSA_PERCENTILE_CONT = 1, QE_OSA_PERCENTILE_DISC = 2, QE_OSA_MODE = 3 };
+typedef struct { int32_t fn; int32_t column; double fraction; } qe_ordered_agg;   /* fraction: the two percentiles only */
+int32_t qe_result_group_ordered(qe_ctx *ctx, const qe_result *result,
+                                const int32_t *group_cols, int32_t ngroup,
+                                const qe_ordered_agg *fns, int32_t nfn, qe_result **out);
+/* what the last qe_result_group_ordered of this context did: out[0] input rows, out[1] groups, out[2] sorts run, out[3] radix
+ * passes of those sorts */
+int32_t qe_ctx_last_ordered_stats(const qe_ctx *ctx, int64_t out[4]);
+
 /* zero-copy: a batch whose columns ARE the result's (not owned; the result must outlive the batch).  Same columns, same
  * validity (NULL where the result has none), same dictionaries, nrows = the result's count (zero rows: a zero-row batch).
  * The batch goes into qe_filter_project / qe_filter_aggregate / qe_filter_groupby like any other: that is how a join is

@@ -9,6 +9,8 @@
 //   qe_comm.cpp      the RCCL exchange step and the concatenation of results
 //   qe_join.cpp      the hash equi-join of two device-resident sides, a result as the next plan's batch
 //   qe_window.cpp    window functions over a result: the sort, the boundary flags, the segmented scans
+//   qe_ordered.cpp   ordered-set aggregates per group (quantiles, COUNT DISTINCT, MODE): one sort per argument column, the
+//                    window's boundary flags, then ranks, compaction and picks over the sorted rows
 #pragma once
 
 #include <memory>

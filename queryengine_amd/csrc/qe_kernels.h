@@ -205,6 +205,44 @@ void launch_win_frame(hipStream_t s, const WinFrameArgs &a);
 void launch_win_shift(hipStream_t s, int width, const void *src, const uint64_t *src_valid, const uint32_t *start, const uint32_t *end,
                       int64_t n, int64_t delta, void *out, uint64_t *out_valid);
 
+// ---- ordered-set aggregates per group over sorted rows (qe_ordered.hip) ----
+// grid caps, in blocks of 256 threads: of the kernels with a lane per bitmap word (one sweep covers 2^21 rows), and of those
+// with a lane per group or per run of equal values (262 144 lanes a sweep)
+constexpr int kOsaWordBlocks = 128, kOsaBlocks = 1024;
+// tiles of kWinTileRows rows (32 words) that launch_osa_word_ranks needs as scratch
+inline int64_t osa_rank_tiles(int64_t n) { return (n + kWinTileRows - 1) / kWinTileRows; }
+// Word ranks of a bitmap of n bits whose bits past n are 0: prefix[w] = set bits of the words before w, w <= ceil(n / 64) (so
+// ceil(n / 64) + 1 entries; the last is the total).  rank(i) = prefix[i >> 6] + popc(word & low_mask(i)).  Fixed shape: per
+// tile of 32 words a count, one workgroup over the tile counts (kWinTripTiles per trip), per word the offset inside its tile.
+// tile_c: osa_rank_tiles(n) u32 of scratch
+void launch_osa_word_ranks(hipStream_t s, const unsigned long long *bits, int64_t n, uint32_t *tile_c, uint32_t *prefix);
+// pos[r] = position of the r-th set bit, pos[total] = n; only entries below `capacity` are written
+void launch_osa_compact(hipStream_t s, const unsigned long long *bits, int64_t n, const uint32_t *prefix, uint32_t *pos, int64_t capacity);
+// The sorted rows of one (group columns, argument) sort as the per-group kernels read them.  Group g is rows [gstart[g],
+// gstart[g + 1]); its argument values are NULL up to first[g] and valid, ascending, from there on.
+struct OsaGroups {
+    long long n, ngroups;
+    const unsigned int *perm;               // source row that stands at sorted position j
+    const unsigned int *gstart;             // ngroups + 1 entries, gstart[ngroups] = n
+    unsigned int *first;                    // ngroups entries: first valid position of the group (gstart[g + 1]: none)
+};
+// first[g] by bisection over `valid` (the argument's validity in sorted order; null: every value valid)
+void launch_osa_first_valid(hipStream_t s, const OsaGroups &g, const unsigned long long *valid);
+// a source-row list per group for gather_column (0xFFFFFFFF: no row).  KEY: the group's first row; DISC: the row of
+// v[max(ceil(fraction * c) - 1, 0)], c = valid values; MODE: the row `best` names (launch_osa_mode)
+enum { QE_OSA_ROWS_KEY = 0, QE_OSA_ROWS_DISC = 1, QE_OSA_ROWS_MODE = 2 };
+void launch_osa_rows(hipStream_t s, const OsaGroups &g, int kind, double fraction, const unsigned long long *best, uint32_t *rows_out);
+// PERCENTILE_CONT: out[g] and its validity word (whole words are written); type / data: the SOURCE column (DOUBLE, INT64, INT32)
+void launch_osa_percentile_cont(hipStream_t s, const OsaGroups &g, int type, const void *data, double fraction, double *out,
+                                unsigned long long *out_valid);
+// COUNT_DISTINCT: out[g] = runs of equal values among the group's valid rows = peer bits in [first[g], gstart[g + 1])
+void launch_osa_count_distinct(hipStream_t s, const OsaGroups &g, const unsigned long long *peer, const uint32_t *peer_prefix, double *out);
+// MODE: best[g] (zeroed by the caller) = max over the group's runs of valid values of (length << 32 | 0xFFFFFFFF - start);
+// 0 = no valid value.  runpos: the compacted peer bits, runs + 1 entries, runs = the total that peer_prefix ends with (read
+// on the device: the grid is sized by n); pstart / pstart_prefix: the group of a position
+void launch_osa_mode(hipStream_t s, const OsaGroups &g, const uint32_t *runpos, const uint32_t *peer_prefix, const unsigned long long *pstart,
+                     const uint32_t *pstart_prefix, unsigned long long *best);
+
 // ---- gathers through u32 row ids (qe_kernels.hip): ORDER BY, window, join, per-node ----
 // grid caps, in blocks of 256 threads: every caller's, and the join's output columns (with the narrow cap the probe was 0.4 to
 // 0.6 % slower than before in every interleaved run, with the wide one it is not: profiles/result_builder_refactor_summary.txt)

@@ -32,6 +32,20 @@ def window_frame_fn(f: Sequence) -> tuple:
     return (f + (0,))[:5]
 
 
+def MEDIAN(column: int) -> tuple:
+    """The median of a column as an entry of Context.group_ordered: PERCENTILE_CONT(0.5) (the ABI has no fifth function)."""
+    return (N.OSA_PERCENTILE_CONT, int(column), 0.5)
+
+
+def ordered_agg(f: Sequence) -> tuple:
+    """(fn, column, fraction) of one ordered-set aggregate entry ``(native.OSA_*, column[, fraction])``; the fraction is read
+    by the two percentiles only and defaults to 0.0."""
+    f = tuple(f)
+    if not 2 <= len(f) <= 3:
+        raise ValueError("an ordered-set aggregate is (fn, column) or (fn, column, fraction)")
+    return (int(f[0]), int(f[1]), float(f[2]) if len(f) == 3 else 0.0)
+
+
 class Context:
     """qe_ctx: one device + one HIP stream.  ``device=None`` -> planning-only (QE_DEVICE_NONE)."""
 
@@ -218,6 +232,25 @@ class Context:
         out = (C.c_int64 * 4)()
         N.check(self.handle, self._lib.qe_ctx_last_window_stats(self.handle, out))
         return {"rows": int(out[0]), "partitions": int(out[1]), "tiles": int(out[2]), "trips": int(out[3])}
+
+    def group_ordered(self, result: "Result", group_by: Sequence[int], functions: Sequence) -> "Result":
+        """qe_result_group_ordered: one row per group of `result`, the groups ascending by the `group_by` columns under the
+        comparator of order_by_keys (NULL first; NOT the insertion order of filter_groupby; no column = one group), the group
+        columns followed by one column per entry of `functions` = [(native.OSA_*, column[, fraction]), ...]: COUNT_DISTINCT,
+        PERCENTILE_CONT(fraction) (bit-exact linear interpolation; ``MEDIAN(column)`` is fraction 0.5), PERCENTILE_DISC(fraction)
+        and MODE (ties: the smallest value) over the group's non-NULL values.  No function: the distinct key tuples."""
+        fns = [ordered_agg(f) for f in functions]
+        arr = (N.OrderedAgg * max(1, len(fns)))(*[N.OrderedAgg(*f) for f in fns])
+        h = C.c_void_p()
+        N.check(self.handle, self._lib.qe_result_group_ordered(self.handle, result.handle, _i32_array(group_by), len(group_by), arr, len(fns),
+                                                               C.byref(h)))
+        return Result(self, h)
+
+    def last_ordered_stats(self) -> dict:
+        """qe_ctx_last_ordered_stats: input rows, groups, sorts run and radix passes of those sorts of the last group_ordered()."""
+        out = (C.c_int64 * 4)()
+        N.check(self.handle, self._lib.qe_ctx_last_ordered_stats(self.handle, out))
+        return {"rows": int(out[0]), "groups": int(out[1]), "sorts": int(out[2]), "radix_passes": int(out[3])}
 
     def concat(self, parts: Sequence["Result"]) -> "Result":
         """qe_result_concat: results of this device, concatenated in the given order."""

@@ -34,6 +34,8 @@ WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_SUM, WIN_COUNT, WIN_MIN, WIN_MAX, 
 WIN_FIRST_VALUE, WIN_LAST_VALUE = 10, 11        # qe_result_window_frames only
 FRAME_UNBOUNDED = -1                             # QE_FRAME_UNBOUNDED: a frame edge at the partition's edge
 WIN_TILE_ROWS, WIN_TRIP_TILES = 2048, 1024   # the scan's tile and the tile aggregates one trip covers
+OSA_COUNT_DISTINCT, OSA_PERCENTILE_CONT, OSA_PERCENTILE_DISC, OSA_MODE = range(4)   # qe_result_group_ordered
+OSA_WORD_BLOCKS, OSA_BLOCKS = 128, 1024      # its grid caps in blocks of 256 lanes: a lane per bitmap word; a lane per group or run
 
 
 class QeError(RuntimeError):
@@ -87,6 +89,11 @@ class WindowFrameFn(C.Structure):
     """qe_window_frame_fn: a window function with its frame, ROWS BETWEEN preceding PRECEDING AND following FOLLOWING
     (each FRAME_UNBOUNDED or a row count; both 0 for the ranks and LAG / LEAD, which ignore the frame)."""
     _fields_ = [("fn", C.c_int32), ("column", C.c_int32), ("offset", C.c_int64), ("preceding", C.c_int64), ("following", C.c_int64)]
+
+
+class OrderedAgg(C.Structure):
+    """qe_ordered_agg: one ordered-set aggregate (column: its argument; fraction: the two percentiles only)."""
+    _fields_ = [("fn", C.c_int32), ("column", C.c_int32), ("fraction", C.c_double)]
 
 
 # every symbol include/qe_hip.h declares: (name, restype, argtypes)
@@ -162,6 +169,8 @@ SYMBOLS = [
     ("qe_result_window", C.c_int32, [_P, _P, C.POINTER(C.c_int32), C.c_int32, _P, C.c_int32, C.POINTER(WindowFn), C.c_int32, C.POINTER(_P)]),
     ("qe_result_window_frames", C.c_int32, [_P, _P, C.POINTER(C.c_int32), C.c_int32, _P, C.c_int32, C.POINTER(WindowFrameFn), C.c_int32, C.POINTER(_P)]),
     ("qe_ctx_last_window_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
+    ("qe_result_group_ordered", C.c_int32, [_P, _P, C.POINTER(C.c_int32), C.c_int32, C.POINTER(OrderedAgg), C.c_int32, C.POINTER(_P)]),
+    ("qe_ctx_last_ordered_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_batch_from_result", C.c_int32, [_P, _P, C.POINTER(_P)]),
     ("qe_comm_unique_id", C.c_int32, [_P, _P]),
     ("qe_comm_init", C.c_int32, [_P, C.c_int32, C.c_int32, _P]),

@@ -12,6 +12,7 @@ There is no CPU evaluation here: expressions only ever run inside libqe_hip.so.
 from __future__ import annotations
 
 import math
+import struct
 from typing import Any, Callable, List, Optional, Sequence
 
 from . import engine as E
@@ -438,6 +439,143 @@ class WindowOperator(Operator):
 
     def result(self) -> E.Result:
         """The windowed columns in HBM (valid until close()); only when the source is a GPU operator."""
+        if self._result is None:
+            raise RuntimeError("Operator not initialized")
+        return self._result
+
+    def next(self) -> Optional[List[Any]]:
+        if self._iter is None:
+            raise RuntimeError("Operator not opened")
+        return next(self._iter, None)
+
+    def close(self) -> None:
+        self._iter = None
+        if self._result is not None:
+            self._result.free()
+            self._result = None
+
+
+def _same_bits(a: float, b: float) -> bool:
+    return struct.pack("<d", a) == struct.pack("<d", b)
+
+
+class OrderedAggregateOperator(Operator):
+    """Ordered-set aggregates per group over a source: one row per group, the groups ASCENDING by the ``group_by`` columns
+    under the comparator of ``OrderByOperator`` (``None`` first; not the insertion order of the GROUP BY operators; no column =
+    the whole source is one group), the group columns followed by one value per entry of ``functions`` =
+    ``[(native.OSA_*, column[, fraction]), ...]``.  No function: the distinct key tuples (SELECT DISTINCT).
+
+    Rows share a group when they compare equal on every group column (``None`` is a key value, all NaNs are one value, -0.0
+    and 0.0 are two).  The values of a group for a column are its non-``None`` values ``v[0..c-1]``, ascending under the same
+    comparator.  COUNT_DISTINCT counts the distinct ones (an int; 0 for none).  PERCENTILE_DISC(q) is
+    ``v[max(ceil(q * float(c)) - 1, 0)]``.  PERCENTILE_CONT(q), numeric columns only, converts to float AFTER sorting and, with
+    ``h = q * float(c - 1)``, ``lo = floor(h)``, ``hi = ceil(h)``, ``frac = h - lo``, is ``v[lo]`` when ``frac == 0`` or
+    ``v[lo]`` and ``v[hi]`` have the same bits, else ``v[lo] + (v[hi] - v[lo]) * frac`` in exactly this order (``engine.MEDIAN``
+    is q = 0.5).  MODE is the value of the longest run of equal values, the smallest of several.  The last three are ``None``
+    for a group without a value.  A source without rows gives no row, or (no group column) one row of 0 and ``None``.
+
+    When the source is a GPU operator (``result()`` and ``ctx``) the rows never leave HBM (qe_result_group_ordered) and the
+    operator offers ``result()`` and ``ctx`` itself.  Any other source is drained and evaluated on the host: stable sorts with
+    ``_compare_key``, then one sequential loop per group -- the executable statement of the semantics, the exact f64 formulas
+    included, and the expectation of the device tests."""
+
+    def __init__(self, source: Operator, group_by: Sequence[int], functions: Sequence):
+        self.source = source
+        self.group_by = [int(c) for c in group_by]
+        self.functions = [E.ordered_agg(f) for f in functions]
+        if len(self.group_by) > 7:
+            raise ValueError("OrderedAggregateOperator: at most 7 group columns")
+        if len(self.functions) > 16:
+            raise ValueError("OrderedAggregateOperator: at most 16 functions")
+        if not self.group_by and not self.functions:
+            raise ValueError("OrderedAggregateOperator: no group column and no function")
+        if any(c < 0 for c in self.group_by) or any(c < 0 for _, c, _ in self.functions):
+            raise ValueError("OrderedAggregateOperator: negative column")
+        for fn, _, fraction in self.functions:
+            if not N.OSA_COUNT_DISTINCT <= fn <= N.OSA_MODE:
+                raise ValueError("OrderedAggregateOperator: unknown function")
+            if fn in (N.OSA_PERCENTILE_CONT, N.OSA_PERCENTILE_DISC) and not 0.0 <= fraction <= 1.0:
+                raise ValueError("OrderedAggregateOperator: a percentile's fraction lies in [0, 1]")
+        self._on_device = hasattr(source, "result") and hasattr(source, "ctx")
+        if self._on_device:
+            self.ctx = source.ctx
+        self._result: Optional[E.Result] = None
+        self._iter = None
+
+    def _device_rows(self):
+        cols = self._result.to_columns()
+        first = len(self.group_by)
+        for i in range(self._result.count):
+            row = [c.value(i) for c in cols]
+            for k, f in enumerate(self.functions):
+                if f[0] == N.OSA_COUNT_DISTINCT:
+                    row[first + k] = int(row[first + k])
+            yield row
+
+    @staticmethod
+    def _evaluate(fn: int, fraction: float, v: List[Any]):
+        """One function over the ascending non-None values of one group."""
+        c = len(v)
+        if fn == N.OSA_COUNT_DISTINCT:
+            return sum(1 for i in range(c) if i == 0 or _compare_key(v[i]) != _compare_key(v[i - 1]))
+        if c == 0:
+            return None
+        if fn == N.OSA_PERCENTILE_DISC:
+            return v[max(math.ceil(fraction * float(c)) - 1, 0)]
+        if fn == N.OSA_PERCENTILE_CONT:
+            h = fraction * float(c - 1)
+            lo, hi = math.floor(h), math.ceil(h)
+            frac = h - float(lo)
+            a, b = float(v[lo]), float(v[hi])
+            if frac == 0.0 or _same_bits(a, b):
+                return a
+            diff = b - a
+            step = diff * frac
+            return a + step
+        best, best_len, begin = None, 0, 0                  # MODE: a later run wins only when it is LONGER
+        for i in range(1, c + 1):
+            if i == c or _compare_key(v[i]) != _compare_key(v[begin]):
+                if i - begin > best_len:
+                    best, best_len = v[begin], i - begin
+                begin = i
+        return best
+
+    def _rows_host(self) -> List[List[Any]]:
+        data = mapTo(self.source, [], lambda row: list(row))
+        for fn, column, _ in self.functions:
+            if fn == N.OSA_PERCENTILE_CONT and any(isinstance(row[column], (bool, str)) for row in data):
+                raise ValueError("OrderedAggregateOperator: PERCENTILE_CONT needs a numeric column")
+        for column in reversed(self.group_by):
+            data.sort(key=lambda row: _compare_key(row[column]))
+        if not data and not self.group_by:
+            return [[self._evaluate(fn, fraction, []) for fn, _, fraction in self.functions]]
+        out = []
+        begin = 0
+        while begin < len(data):
+            end = begin + 1
+            while end < len(data) and all(_compare_key(data[end][c]) == _compare_key(data[begin][c]) for c in self.group_by):
+                end += 1
+            row = [data[begin][c] for c in self.group_by]
+            for fn, column, fraction in self.functions:
+                v = sorted((r[column] for r in data[begin:end] if r[column] is not None), key=_compare_key)
+                row.append(self._evaluate(fn, fraction, v))
+            out.append(row)
+            begin = end
+        return out
+
+    def open(self) -> None:
+        if self._on_device:
+            self.source.open()
+            try:
+                self._result = self.ctx.group_ordered(self.source.result(), self.group_by, self.functions)
+            finally:
+                self.source.close()
+            self._iter = self._device_rows()
+        else:
+            self._iter = iter(self._rows_host())
+
+    def result(self) -> E.Result:
+        """The groups in HBM (valid until close()); only when the source is a GPU operator."""
         if self._result is None:
             raise RuntimeError("Operator not initialized")
         return self._result
