@@ -485,7 +485,9 @@ void parallel_read(TextSource &src, char *dst, size_t off, size_t n) {
         src.read_at(dst, off, n);
         return;
     }
-    const size_t per = ((n / nthr) + 4095) & ~(size_t)4095;
+    // whole pages per thread, rounded UP twice: n / nthr rounded down leaves the last n % nthr bytes to nobody when it is a
+    // whole number of pages already
+    const size_t per = (((n + nthr - 1) / nthr) + 4095) & ~(size_t)4095;
     std::vector<std::thread> ts;
     std::vector<std::string> errs(nthr);
     for (unsigned t = 1; t < nthr; t++) {

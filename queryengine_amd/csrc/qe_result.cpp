@@ -95,7 +95,7 @@ static void parallel_memcpy(void *dst, const void *src, size_t n) {
         return;
     }
     std::vector<std::thread> ts;
-    const size_t per = ((n / nthr) + 4095) & ~(size_t)4095;
+    const size_t per = (((n + nthr - 1) / nthr) + 4095) & ~(size_t)4095;   // rounded up twice: nthr * per >= n
     for (unsigned t = 1; t < nthr; t++) {
         const size_t off = (size_t)t * per;
         if (off >= n) break;
