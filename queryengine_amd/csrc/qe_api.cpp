@@ -11,7 +11,7 @@
 #include "qe_exec.h"
 #include "qe_kernels.h"
 #include "qe_pernode.h"
-#include "qe_pernode_kernels.h"
+#include "qe_scan.h"
 
 using namespace qe;
 
@@ -686,10 +686,9 @@ int64_t run_local(const FusedRun &r, double sel) {
     QE_HIP(hipModuleGetFunction(&f_scan, plan.kernel.module, "qe_fl_scan"));
     QE_HIP(hipModuleGetFunction(&f_move, plan.kernel.module, "qe_fl_move"));
     PoolScratch scratch(ctx);
-    const int64_t nsum = (nchunks + 1023) / 1024;
     uint32_t *d_counts = (uint32_t *)scratch.alloc((size_t)nchunks * 4);
     uint32_t *d_offsets = (uint32_t *)scratch.alloc((size_t)nchunks * 4);
-    uint32_t *d_sums = (uint32_t *)scratch.alloc((size_t)(nsum + 1) * 4);
+    uint32_t *d_sums = (uint32_t *)scratch.alloc((size_t)scan_blocks(nchunks) * 4);
     FusedParams lp = r.p;
     alloc_staging(r, scratch, lp, (size_t)nchunks * (size_t)ring);
     lp.capacity = r.cap;
@@ -715,7 +714,7 @@ int64_t run_local(const FusedRun &r, double sel) {
     const unsigned int *hc = with_ctrl_block(ctx, [&] {
         if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         QE_HIP(hipModuleLaunchKernel(f_scan, grid, 1, 1, plan.geo.threads, 1, 1, 0, ctx->stream, largs, nullptr));
-        pn::exclusive_scan_u32(ctx->stream, d_counts, d_offsets, d_sums, nchunks, lp.total);
+        exclusive_scan<uint32_t>(ctx->stream, ArrayLoad<uint32_t>{d_counts}, d_offsets, d_sums, nchunks, lp.total);
         QE_HIP(hipModuleLaunchKernel(f_move, mgrid, 1, 1, 256, 1, 1, 0, ctx->stream, largs, nullptr));
         if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     });
@@ -787,7 +786,7 @@ int64_t run_two_pass(const FusedRun &r) {
     with_ctrl_block(ctx, [&] {
         if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         QE_HIP(hipModuleLaunchKernel(f_count, grid, 1, 1, plan.geo.threads, 1, 1, 0, ctx->stream, args, nullptr));
-        launch_gb_scan(ctx->stream, d_counts, nchunks, 1, p.total);   // counts -> exclusive offsets, *total = kept rows
+        launch_carry_scan<uint32_t, 256>(ctx->stream, d_counts, nchunks, 1, p.total);   // counts -> exclusive offsets, *total = kept rows
         QE_HIP(hipModuleLaunchKernel(f_write, grid, 1, 1, plan.geo.threads, 1, 1, 0, ctx->stream, args, nullptr));
         if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     });

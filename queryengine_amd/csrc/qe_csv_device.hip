@@ -30,6 +30,7 @@
 
 #include "qe_exec.h"
 #include "qe_csv_number.h"
+#include "qe_scan.h"
 
 using i64 = long long;
 using u64 = unsigned long long;
@@ -38,48 +39,12 @@ using u32 = unsigned int;
 namespace {
 
 constexpr int kTile = 4096;          // text bytes per wave in the structure passes (64 steps of 64 bytes)
-constexpr int kScanPer = 2048;       // elements per workgroup of the scan (256 threads x 8)
 constexpr u32 kEmpty = 0xFFFFFFFFu;
 
 // what the structure pass found that the host parser would read differently
 enum { F_QUOTE_RULE = 1, F_BAD_NUMBER = 2, F_PATCH_OVERFLOW = 4 };
 
 __device__ inline bool is_sep(unsigned char c) { return c == ',' || c == '\n' || c == '\r' || c == '"'; }
-
-// ---- exclusive sum scan over i64, in place ------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) scan_local_kernel(i64 *a, i64 n, i64 *sums) {
-    __shared__ i64 wsum[4];
-    const i64 base = (i64)blockIdx.x * kScanPer + (i64)threadIdx.x * 8;
-    i64 v[8];
-    i64 s = 0;
-    for (int j = 0; j < 8; j++) {
-        v[j] = base + j < n ? a[base + j] : 0;
-        s += v[j];
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    i64 incl = s;
-    for (int d = 1; d < 64; d <<= 1) {
-        const i64 t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    i64 off = 0;
-    for (int k = 0; k < w; k++) off += wsum[k];
-    i64 excl = off + incl - s;
-    for (int j = 0; j < 8; j++) {
-        if (base + j < n) a[base + j] = excl;
-        excl += v[j];
-    }
-    if (threadIdx.x == 255) sums[blockIdx.x] = off + incl;
-}
-
-__global__ void __launch_bounds__(256) scan_add_kernel(i64 *a, i64 n, const i64 *sums) {
-    const i64 add = sums[blockIdx.x];
-    const i64 base = (i64)blockIdx.x * kScanPer;
-    for (int j = threadIdx.x; j < kScanPer; j += 256)
-        if (base + j < n) a[base + j] += add;
-}
 
 // ---- 1. quotes per tile ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) quote_count_kernel(const unsigned char *text, i64 ntiles, i64 *tile_quotes) {
@@ -120,7 +85,7 @@ __global__ void __launch_bounds__(256) records_kernel(const unsigned char *text,
     for (int s = 0; s < kTile / 64; s++) {
         const i64 i = base + s * 64 + lane;
         const unsigned char c = i < n ? text[i] : 0;
-        unsigned char prev = (unsigned char)__shfl_up((int)c, 1, 64);
+        unsigned char prev = (unsigned char)qe::wave_prev((int)c);
         if (lane == 0) prev = carry_prev;
         carry_prev = (unsigned char)__shfl((int)c, 63, 64);
         const u64 qm = __ballot(c == '"');
@@ -410,15 +375,7 @@ T *dev_array(PoolScratch &S, size_t n) { return (T *)S.alloc(n * sizeof(T)); }
 
 // exclusive sum of a[0..n) in place; a must hold n + 1 elements, a[n] = 0 on entry: the total lands in a[n]
 void scan(qe_ctx *ctx, PoolScratch &S, i64 *a, i64 n) {
-    const i64 m = n + 1;
-    const unsigned nb = grid_of(m, kScanPer);
-    i64 *sums = dev_array<i64>(S, (size_t)nb + 1);
-    hipLaunchKernelGGL(scan_local_kernel, dim3(nb), dim3(256), 0, ctx->stream, a, m, sums);
-    if (nb > 1) {
-        QE_HIP(hipMemsetAsync(sums + nb, 0, sizeof(i64), ctx->stream));
-        scan(ctx, S, sums, nb);
-        hipLaunchKernelGGL(scan_add_kernel, dim3(nb), dim3(256), 0, ctx->stream, a, m, (const i64 *)sums);
-    }
+    exclusive_scan<i64>(ctx->stream, ArrayLoad<i64>{a}, a, dev_array<i64>(S, (size_t)scan_blocks(n + 1)), n + 1, nullptr);
 }
 
 template <typename T>

@@ -8,6 +8,7 @@
 
 #include "qe_exec.h"
 #include "qe_kernels.h"
+#include "qe_scan.h"
 
 using namespace qe;
 
@@ -426,7 +427,7 @@ qe_result *run_groupby_hp(qe_ctx *ctx, const qe_batch *batch, const std::shared_
     void *args[] = {&p};
     if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     QE_HIP(hipModuleLaunchKernel(f_count, grid, 1, 1, plan->geo.threads, 1, 1, 0, ctx->stream, args, nullptr));
-    launch_gb_scan(ctx->stream, d_counts, nchunks, P, d_start);
+    launch_carry_scan<uint32_t, 256>(ctx->stream, d_counts, nchunks, P, d_start);
     std::vector<unsigned long long> start((size_t)P + 1, 0);
     QE_HIP(hipMemcpyAsync(start.data(), d_start, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
     QE_HIP(hipStreamSynchronize(ctx->stream));
@@ -559,7 +560,7 @@ qe_result *run_groupby_dense(qe_ctx *ctx, const qe_batch *batch, const std::shar
         void *args[] = {&p};
         if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         QE_HIP(hipModuleLaunchKernel(f_count, grid, 1, 1, plan->geo.threads, 1, 1, 0, ctx->stream, args, nullptr));
-        launch_gb_scan(ctx->stream, d_counts, nchunks, P, d_start);
+        launch_carry_scan<uint32_t, 256>(ctx->stream, d_counts, nchunks, P, d_start);
         std::vector<unsigned long long> start((size_t)P + 1, 0);
         QE_HIP(hipMemcpyAsync(start.data(), d_start, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
         QE_HIP(hipStreamSynchronize(ctx->stream));

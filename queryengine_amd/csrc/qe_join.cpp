@@ -6,6 +6,7 @@
 
 #include "qe_exec.h"
 #include "qe_kernels.h"
+#include "qe_scan.h"
 
 namespace qe {
 namespace {
@@ -213,7 +214,7 @@ qe_result *probe_table(qe_ctx *ctx, const qe_join_table *t, const qe_join_input 
     pa.longest = (uint32_t *)(d_ctl + 1);
     QE_HIP(hipMemsetAsync(d_ctl, 0, 16, ctx->stream));
     launch_join_count(ctx->stream, pa);
-    launch_join_scan(ctx->stream, pa.blocksum, nblocks, d_ctl);
+    launch_carry_scan<unsigned long long, 1024>(ctx->stream, pa.blocksum, nblocks, 1, d_ctl);   // 64-bit: the pairs may pass 2^32
     unsigned long long h_ctl[2] = {0, 0};
     QE_HIP(hipMemcpyAsync(h_ctl, d_ctl, 16, hipMemcpyDeviceToHost, ctx->stream));   // the one read-back: the output's size
     QE_HIP(hipGetLastError());

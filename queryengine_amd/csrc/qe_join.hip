@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "qe_kernels.h"
+#include "qe_scan.h"
 
 namespace qe {
 
@@ -177,50 +178,13 @@ __global__ void __launch_bounds__(256) join_count_kernel(const JoinProbeArgs a) 
     if (threadIdx.x == 0) a.blocksum[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
 }
 
-// exclusive 64-bit scan of the block sums by ONE workgroup; *total = their sum
-__global__ void __launch_bounds__(1024) join_scan_kernel(u64 *sums, i64 n, u64 *total) {
-    __shared__ u64 s_wave[16];
-    __shared__ u64 s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (i64 b = 0; b < n; b += 1024) {
-        const i64 i = b + threadIdx.x;
-        const u64 v = i < n ? sums[i] : 0ull;
-        u64 incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const u64 t = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += t;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        u64 before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < n) sums[i] = before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = before + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = s_carry;
-}
-
 // pass 2: the pairs of probe row i at offset (block offset + the counts of the rows before it in its block)
 __global__ void __launch_bounds__(256) join_write_kernel(const JoinProbeArgs a) {
     __shared__ u64 s_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     const u32 cnt = i < a.n ? a.cnt[i] : 0u;
-    u64 incl = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    u64 off = a.blocksum[blockIdx.x] + incl - cnt;
-    for (int w = 0; w < wave; ++w) off += s_wave[w];
+    u64 block_total;
+    const u64 off = a.blocksum[blockIdx.x] + block_excl_scan<u64, 256>((u64)cnt, s_wave, block_total);
     if (cnt == 0) return;
     if (off + cnt > a.total) return;   // cannot happen: the lists hold exactly `total` pairs
     if (!a.brow_out) {   // SEMI / ANTI
@@ -273,10 +237,6 @@ int64_t join_probe_blocks(int64_t n) { return (n + 255) / 256; }
 void launch_join_count(hipStream_t s, const JoinProbeArgs &a) {
     if (a.n <= 0) return;
     hipLaunchKernelGGL(join_count_kernel, dim3((unsigned)join_probe_blocks(a.n)), dim3(256), 0, s, a);
-}
-
-void launch_join_scan(hipStream_t s, unsigned long long *blocksum, int64_t nblocks, unsigned long long *total) {
-    hipLaunchKernelGGL(join_scan_kernel, dim3(1), dim3(1024), 0, s, (u64 *)blocksum, (i64)nblocks, (u64 *)total);
 }
 
 void launch_join_write(hipStream_t s, const JoinProbeArgs &a) {

@@ -18,11 +18,6 @@ void launch_stream_read(hipStream_t s, const void *src, int64_t nbytes, unsigned
 void launch_stream_read_write(hipStream_t s, const void *src, int64_t nbytes, unsigned long long *sink, void *dst,
                               int64_t dst_bytes, int write_every, int window_period, int window_len, int blocks_per_event);
 
-// ---- partitioned group-by (domains that do not fit LDS) ----
-// counts[chunk][part] (kept rows) -> in place: offset of (chunk, part) inside its partition; totals[part] = rows of the partition
-void launch_gb_scan(hipStream_t s, uint32_t *counts, int64_t nchunks, int nparts, unsigned long long *totals);
-
-
 // hashed group-by: fill a table of nentries entries with the per-word pattern of an empty entry; copy the entries in use
 // (state word == 2) to a dense array, *counter = how many
 struct HtInit {
@@ -129,14 +124,13 @@ struct JoinProbeArgs {
     int join_type;                          // QE_JOIN_*
     unsigned int *cnt;                      // output rows of probe row i
     unsigned int *first;                    // sorted entry of its first match (0xFFFFFFFF: none); null for SEMI / ANTI
-    unsigned long long *blocksum;           // per block of 256 probe rows: pass 1 writes the sum, launch_join_scan the offset
+    unsigned long long *blocksum;           // per block of 256 probe rows: pass 1 writes the sum, the carry scan (qe_scan.h) the offset
     unsigned int *longest;                  // max over the probe rows of the entries one row walked
     unsigned long long total;               // pass 2: pairs the lists hold
     unsigned int *prow_out, *brow_out;      // pass 2: the pairs (brow_out null for SEMI / ANTI; build row 0xFFFFFFFF = none)
 };
 int64_t join_probe_blocks(int64_t n);       // entries of blocksum
 void launch_join_count(hipStream_t s, const JoinProbeArgs &a);
-void launch_join_scan(hipStream_t s, unsigned long long *blocksum, int64_t nblocks, unsigned long long *total);
 void launch_join_write(hipStream_t s, const JoinProbeArgs &a);
 
 // ---- window functions over a sorted result (qe_window.hip) ----
@@ -206,18 +200,10 @@ void launch_win_shift(hipStream_t s, int width, const void *src, const uint64_t 
                       int64_t n, int64_t delta, void *out, uint64_t *out_valid);
 
 // ---- ordered-set aggregates per group over sorted rows (qe_ordered.hip) ----
-// grid caps, in blocks of 256 threads: of the kernels with a lane per bitmap word (one sweep covers 2^21 rows), and of those
-// with a lane per group or per run of equal values (262 144 lanes a sweep)
-constexpr int kOsaWordBlocks = 128, kOsaBlocks = 1024;
-// tiles of kWinTileRows rows (32 words) that launch_osa_word_ranks needs as scratch
-inline int64_t osa_rank_tiles(int64_t n) { return (n + kWinTileRows - 1) / kWinTileRows; }
-// Word ranks of a bitmap of n bits whose bits past n are 0: prefix[w] = set bits of the words before w, w <= ceil(n / 64) (so
-// ceil(n / 64) + 1 entries; the last is the total).  rank(i) = prefix[i >> 6] + popc(word & low_mask(i)).  Fixed shape: per
-// tile of 32 words a count, one workgroup over the tile counts (kWinTripTiles per trip), per word the offset inside its tile.
-// tile_c: osa_rank_tiles(n) u32 of scratch
-void launch_osa_word_ranks(hipStream_t s, const unsigned long long *bits, int64_t n, uint32_t *tile_c, uint32_t *prefix);
-// pos[r] = position of the r-th set bit, pos[total] = n; only entries below `capacity` are written
-void launch_osa_compact(hipStream_t s, const unsigned long long *bits, int64_t n, const uint32_t *prefix, uint32_t *pos, int64_t capacity);
+// grid cap, in blocks of 256 threads, of the kernels with a lane per group or per run of equal values (262 144 lanes a sweep)
+constexpr int kOsaBlocks = 1024;
+// The word ranks (`*_prefix`) and the compacted positions (gstart, runpos) below come from bitmap_ranks / bitmap_positions
+// (qe_scan.h): prefix[w] = set bits of the words before w, ceil(n / 64) + 1 entries, the last is the total.
 // The sorted rows of one (group columns, argument) sort as the per-group kernels read them.  Group g is rows [gstart[g],
 // gstart[g + 1]); its argument values are NULL up to first[g] and valid, ascending, from there on.
 struct OsaGroups {

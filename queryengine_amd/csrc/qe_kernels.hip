@@ -240,42 +240,6 @@ void launch_stream_read(hipStream_t s, const void *src, int64_t nbytes, unsigned
         hipLaunchKernelGGL(stream_read_kernel, dim3(256 * (wgs_per_cu > 0 ? wgs_per_cu : 8)), dim3(256), 0, s, (const u64x2 *)src, nvec, (u64 *)sink);
 }
 
-// ---- partitioned group-by -------------------------------------------------------------------------------------------
-// One workgroup per partition walks the chunks in order: exclusive scan of counts[chunk][part] along the chunk axis.
-__global__ void __launch_bounds__(256) gb_scan_kernel(u32 *counts, i64 nchunks, int nparts, u64 *totals) {
-    __shared__ u32 s_wave[4];
-    const int part = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 running = 0;
-    for (i64 c0 = 0; c0 < nchunks; c0 += 256) {
-        const i64 c = c0 + threadIdx.x;
-        const u32 v = c < nchunks ? counts[c * nparts + part] : 0u;
-        u32 incl = v;   // inclusive scan inside the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const u32 t = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += t;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        u32 before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) before += s_wave[w];
-            total += s_wave[w];
-        }
-        if (c < nchunks) counts[c * nparts + part] = (u32)(running + before + incl - v);
-        running += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) totals[part] = running;
-}
-
-void launch_gb_scan(hipStream_t s, uint32_t *counts, int64_t nchunks, int nparts, unsigned long long *totals) {
-    if (nparts <= 0) return;
-    hipLaunchKernelGGL(gb_scan_kernel, dim3((unsigned)nparts), dim3(256), 0, s, counts, (i64)nchunks, nparts, (u64 *)totals);
-}
-
 // ---- bitmap segments (result concatenation / gather) -----------------------------------------------------------------
 // Place `nbits` bits of `src` (bit i = word i>>6, bit i&63) at bit offset `dst_off` of `dst`.  One thread owns one
 // destination word, so the read-modify-write of the two boundary words is race free inside a launch; segments are placed

@@ -7,6 +7,7 @@
 
 #include "qe_exec.h"
 #include "qe_kernels.h"
+#include "qe_scan.h"
 
 namespace qe {
 namespace {
@@ -80,7 +81,7 @@ qe_result *run_group_ordered(qe_ctx *ctx, const qe_result *src, const int32_t *g
     unsigned long long *pstart = (unsigned long long *)sc.alloc(bitmap_bytes(n));
     unsigned long long *peer = (unsigned long long *)sc.alloc(bitmap_bytes(n));
     unsigned long long *d_ngroups = (unsigned long long *)sc.alloc(16);
-    uint32_t *tile_c = (uint32_t *)sc.alloc((size_t)osa_rank_tiles(n) * 4);
+    uint32_t *sums = (uint32_t *)sc.alloc((size_t)scan_blocks(nwords + 1) * 4);
     uint32_t *pstart_prefix = (uint32_t *)sc.alloc((size_t)(nwords + 1) * 4);
     ResultPtr res = own_result(ctx, nullptr);
     int64_t G = 0;
@@ -140,8 +141,8 @@ qe_result *run_group_ordered(qe_ctx *ctx, const qe_result *src, const int32_t *g
         stats[3] += drv.radix_passes;
 
         // ---- group starts; the key columns come from the first sort ----
-        launch_osa_word_ranks(ctx->stream, pstart, n, tile_c, pstart_prefix);
-        launch_osa_compact(ctx->stream, pstart, n, pstart_prefix, gstart, G + 1);
+        bitmap_ranks(ctx->stream, (const uint64_t *)pstart, nullptr, n, pstart_prefix, sums, nullptr);
+        bitmap_positions(ctx->stream, (const uint64_t *)pstart, nullptr, n, pstart_prefix, gstart, G + 1, true);
         OsaGroups og{};
         og.n = n;
         og.ngroups = G;
@@ -176,12 +177,12 @@ qe_result *run_group_ordered(qe_ctx *ctx, const qe_result *src, const int32_t *g
         unsigned long long *best = nullptr;
         if (need_ranks) {
             peer_prefix = (uint32_t *)ss.alloc((size_t)(nwords + 1) * 4);
-            launch_osa_word_ranks(ctx->stream, peer, n, tile_c, peer_prefix);
+            bitmap_ranks(ctx->stream, (const uint64_t *)peer, nullptr, n, peer_prefix, sums, nullptr);
         }
         if (need_runs) {   // every MODE of this argument is the same row list
             uint32_t *runpos = (uint32_t *)ss.alloc((size_t)(n + 1) * 4);
             best = (unsigned long long *)ss.alloc((size_t)G * 8);
-            launch_osa_compact(ctx->stream, peer, n, peer_prefix, runpos, n + 1);
+            bitmap_positions(ctx->stream, (const uint64_t *)peer, nullptr, n, peer_prefix, runpos, n + 1, true);
             QE_HIP(hipMemsetAsync(best, 0, (size_t)G * 8, ctx->stream));
             launch_osa_mode(ctx->stream, og, runpos, peer_prefix, pstart, pstart_prefix, best);
         }

@@ -3,10 +3,9 @@
 // The rows arrive sorted by (group columns, argument) and marked by launch_win_flags: pstart = a group starts, peer = a run of
 // equal argument values starts (the NULL run in front of a group included).  What is left is the step from "sorted rows plus
 // two bitmaps" to "one row per group":
-//   word ranks   exclusive prefix of the per-word popcounts of a bitmap, so that rank(i) = set bits below i is O(1).  Fixed
-//                shape like the window scans: a count per tile of 32 words (2048 rows), ONE workgroup over the tile counts
-//                (kWinTripTiles per trip), then the offset of every word inside its tile
+//   word ranks   exclusive prefix of the per-word popcounts of a bitmap, so that rank(i) = set bits below i is O(1)
 //   compaction   every word scatters the positions of its set bits to prefix[word] + k: the group starts, the run starts
+//                (both are the shared bitmap_ranks / bitmap_positions of qe_scan.h, called by qe_ordered.cpp)
 //   first valid  inside a group the argument's validity is 0..01..1 (NULL sorts first): one lane per group bisects
 //   picks        a u32 source-row list per group that the existing gather turns into the output column (keys,
 //                PERCENTILE_DISC, MODE); PERCENTILE_CONT reads its two rows and interpolates; COUNT_DISTINCT is a difference
@@ -17,12 +16,12 @@
 #include <hip/hip_runtime.h>
 
 #include "qe_kernels.h"
+#include "qe_scan.h"
 #include "qe_sort_image.h"
 
 namespace qe {
 
 constexpr u32 kOsaNoRow = 0xFFFFFFFFu;
-constexpr int kOsaTileWords = kWinTileRows / 64;   // 32: half a wave
 
 static unsigned osa_grid(i64 lanes, int max_blocks) {
     const i64 blocks = (lanes + 255) / 256;
@@ -33,95 +32,6 @@ static unsigned osa_grid(i64 lanes, int max_blocks) {
 __device__ __forceinline__ u32 osa_rank(const u64 *bits, const u32 *prefix, i64 i) {
     const int b = (int)(i & 63);
     return prefix[i >> 6] + (b ? (u32)__popcll(bits[i >> 6] & ((1ull << b) - 1ull)) : 0u);
-}
-
-// ---- word ranks ----------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) osa_tile_counts_kernel(const u64 *bits, i64 nwords, u32 *tile_c) {
-    const i64 padded = (nwords + 63) & ~63ll;   // whole waves for the shuffles
-    const i64 stride = (i64)gridDim.x * 256;
-    for (i64 w = (i64)blockIdx.x * 256 + threadIdx.x; w < padded; w += stride) {
-        u32 c = w < nwords ? (u32)__popcll(bits[w]) : 0u;
-#pragma unroll
-        for (int d = 1; d < kOsaTileWords; d <<= 1) c += __shfl_xor(c, d, 64);   // stays inside the half wave
-        if ((threadIdx.x & (kOsaTileWords - 1)) == 0 && w < nwords) tile_c[w / kOsaTileWords] = c;
-    }
-}
-
-// exclusive scan of the tile counts in place, by one workgroup; *total = their sum
-__global__ void __launch_bounds__(kWinTripTiles) osa_tile_scan_kernel(u32 *tile_c, i64 ntiles, u32 *total) {
-    __shared__ u32 s_wave[kWinTripTiles / 64];
-    __shared__ u32 s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0u;
-    __syncthreads();
-    for (i64 b = 0; b < ntiles; b += kWinTripTiles) {
-        const i64 i = b + threadIdx.x;
-        const u32 x = i < ntiles ? tile_c[i] : 0u;
-        u32 incl = x;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const u32 y = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += y;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        u32 before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < ntiles) tile_c[i] = before + incl - x;
-        __syncthreads();   // every lane has read the carry and the wave sums of this trip
-        if (threadIdx.x == kWinTripTiles - 1) s_carry = before + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = s_carry;
-}
-
-__global__ void __launch_bounds__(256) osa_word_prefix_kernel(const u64 *bits, i64 nwords, const u32 *tile_off, u32 *prefix) {
-    const i64 padded = (nwords + 63) & ~63ll;
-    const i64 stride = (i64)gridDim.x * 256;
-    const int sub = threadIdx.x & (kOsaTileWords - 1);
-    for (i64 w = (i64)blockIdx.x * 256 + threadIdx.x; w < padded; w += stride) {
-        const u32 c = w < nwords ? (u32)__popcll(bits[w]) : 0u;
-        u32 incl = c;
-#pragma unroll
-        for (int d = 1; d < kOsaTileWords; d <<= 1) {
-            const u32 y = __shfl_up(incl, d, kOsaTileWords);
-            if (sub >= d) incl += y;
-        }
-        if (w < nwords) prefix[w] = tile_off[w / kOsaTileWords] + incl - c;
-    }
-}
-
-void launch_osa_word_ranks(hipStream_t s, const unsigned long long *bits, int64_t n, uint32_t *tile_c, uint32_t *prefix) {
-    if (n <= 0) return;
-    const i64 nwords = (n + 63) / 64, ntiles = osa_rank_tiles(n);
-    const dim3 g(osa_grid(nwords, kOsaWordBlocks));
-    hipLaunchKernelGGL(osa_tile_counts_kernel, g, dim3(256), 0, s, (const u64 *)bits, nwords, tile_c);
-    hipLaunchKernelGGL(osa_tile_scan_kernel, dim3(1), dim3(kWinTripTiles), 0, s, tile_c, ntiles, prefix + nwords);
-    hipLaunchKernelGGL(osa_word_prefix_kernel, g, dim3(256), 0, s, (const u64 *)bits, nwords, (const u32 *)tile_c, prefix);
-}
-
-// ---- bit compaction ------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) osa_compact_kernel(const u64 *bits, i64 nwords, i64 n, const u32 *prefix, u32 *pos, i64 capacity) {
-    const i64 stride = (i64)gridDim.x * 256;
-    for (i64 w = (i64)blockIdx.x * 256 + threadIdx.x; w < nwords; w += stride) {
-        u64 x = bits[w];
-        i64 at = prefix[w];
-        while (x) {   // at most 64 trips, over this lane's own word
-            if (at < capacity) pos[at] = (u32)(w * 64 + __builtin_ctzll(x));
-            x &= x - 1;
-            ++at;
-        }
-        if (w == 0) {
-            const i64 total = prefix[nwords];
-            if (total < capacity) pos[total] = (u32)n;
-        }
-    }
-}
-void launch_osa_compact(hipStream_t s, const unsigned long long *bits, int64_t n, const uint32_t *prefix, uint32_t *pos, int64_t capacity) {
-    if (n <= 0) return;
-    const i64 nwords = (n + 63) / 64;
-    hipLaunchKernelGGL(osa_compact_kernel, dim3(osa_grid(nwords, kOsaWordBlocks)), dim3(256), 0, s, (const u64 *)bits, nwords, (i64)n, prefix, pos,
-                       (i64)capacity);
 }
 
 // ---- first valid row per group ---------------------------------------------------------------------------------------------
@@ -278,7 +188,7 @@ __global__ void __launch_bounds__(256) osa_mode_kernel(const OsaGroups a, const 
             const u32 og = __shfl_down(g, d, 64);
             if (lane + d < 64 && og == g && ok > key) key = ok;
         }
-        const u32 pg = __shfl_up(g, 1, 64);
+        const u32 pg = wave_prev(g);
         const bool head = lane == 0 || pg != g;
         // read first: the atomic is issued only by a wave that would raise the value
         if (head && key != 0ull && best[g] < key) atomicMax(&best[g], key);

@@ -24,6 +24,7 @@
 #include "qe_exec.h"
 #include "qe_kernels.h"
 #include "qe_pernode_kernels.h"
+#include "qe_scan.h"
 
 namespace qe {
 
@@ -534,9 +535,8 @@ qe_result *run_per_node(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filte
             acc = x.and_valid(acc, keep);
             // 2. kept rows of the current domain
             const int64_t nw = bitmap_words(x.n);
-            Buf counts = x.alloc((size_t)nw * 4), offsets = x.alloc((size_t)nw * 4), sums = x.alloc((size_t)((nw + 1023) / 1024) * 4 + 16);
-            pn::word_popcounts(x.s, (const uint64_t *)acc.get(), nullptr, x.n, (uint32_t *)counts.get(), nw);
-            pn::exclusive_scan_u32(x.s, (const uint32_t *)counts.get(), (uint32_t *)offsets.get(), (uint32_t *)sums.get(), nw, d_total);
+            Buf offsets = x.alloc((size_t)(nw + 1) * 4), sums = x.alloc((size_t)scan_blocks(nw + 1) * 4);
+            bitmap_ranks(x.s, (const uint64_t *)acc.get(), nullptr, x.n, (uint32_t *)offsets.get(), (uint32_t *)sums.get(), d_total);
             QE_HIP(hipMemcpyAsync(ctx->h_ctrl, ctx->d_ctrl, 16, hipMemcpyDeviceToHost, x.s));
             QE_HIP(hipGetLastError());
             QE_HIP(hipStreamSynchronize(x.s));
@@ -547,7 +547,7 @@ qe_result *run_per_node(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filte
             if (kept == x.n) { acc.reset(); continue; }           // everything survived: the domain stays as it is
             if (!last && kept * 2 > x.n) continue;                // not selective enough to pay for a compaction yet: keep the mask
             Buf rel = x.alloc((size_t)std::max<int64_t>(kept, 1) * 4);
-            pn::expand_indices(x.s, (const uint64_t *)acc.get(), nullptr, x.n, (const uint32_t *)offsets.get(), (uint32_t *)rel.get(), nw);
+            bitmap_positions(x.s, (const uint64_t *)acc.get(), nullptr, x.n, (const uint32_t *)offsets.get(), (uint32_t *)rel.get(), kept, false);
             x.narrow(rel, kept);
             acc.reset();
         }

@@ -38,12 +38,6 @@ void kleene(hipStream_t s, bool is_and, const uint64_t *va, const uint64_t *ka, 
 // IF: out = cond ? t : e for value columns; for bitmaps use select_words
 void select(hipStream_t s, int type, const uint64_t *cond, Opnd t, Opnd e, void *out, int64_t n);
 void select_words(hipStream_t s, const uint64_t *cond, const uint64_t *t, const uint64_t *e, uint64_t *out, int64_t nwords);
-// selection vector: keep bitmap (& optional known bitmap) -> ascending row ids (stable compaction)
-void word_popcounts(hipStream_t s, const uint64_t *v, const uint64_t *k, int64_t n, uint32_t *counts, int64_t nwords);
-void exclusive_scan_u32(hipStream_t s, const uint32_t *in, uint32_t *out, uint32_t *block_sums, int64_t n,
-                        unsigned long long *total);
-void expand_indices(hipStream_t s, const uint64_t *v, const uint64_t *k, int64_t n, const uint32_t *word_offsets,
-                    uint32_t *indices, int64_t nwords);
 // gather of up to 8 value columns (4- or 8-byte elements) at the kept row ids in ONE launch (the ids are read once)
 struct GatherArgs {
     const void *src[8];

@@ -1,7 +1,7 @@
 // qe_pernode_kernels.hip -- one precompiled gfx950 kernel per expression node kind
 // (SURVEY 2.1 kernel inventory): arithmetic, negate, cast, comparison -> bitmap via
-// __ballot, Kleene logic on 64-row words, IF select, and the filter's stable
-// compaction (word popcount -> scan -> index expansion -> gather).
+// __ballot, Kleene logic on 64-row words, IF select, and the gather behind the
+// filter's stable compaction (bitmap_ranks -> bitmap_positions of qe_scan.h -> gather).
 //
 // Semantics per node follow evaluator/Interpreter.kt:94-107 (JVM DADD..DREM,
 // Double.compare / equals) exactly as the fused kernels do; validity is handled
@@ -487,138 +487,6 @@ __global__ void __launch_bounds__(256) k_select_words(const u64 *c, const u64 *t
 void select_words(hipStream_t s, const uint64_t *c, const uint64_t *t, const uint64_t *e, uint64_t *out, int64_t nw) {
     if (nw <= 0) return;
     hipLaunchKernelGGL(k_select_words, dim3(grid_for(nw)), dim3(256), 0, s, (const u64 *)c, (const u64 *)t, (const u64 *)e, (u64 *)out, (i64)nw);
-}
-
-// ---- filter: bitmap -> ascending row ids (stable) -------------------------------------------------------------
-__device__ __forceinline__ u64 keep_word(const u64 *v, const u64 *k, i64 w, i64 n) {
-    u64 x = v[w];
-    if (k) x &= k[w];                               // FilterOperator.kt:20: non-null AND true
-    const i64 rem = n - w * 64;
-    if (rem < 64) x &= (1ull << rem) - 1ull;        // bits past the last row
-    return x;
-}
-__global__ void __launch_bounds__(256) k_word_popcounts(const u64 *v, const u64 *k, i64 n, u32 *counts, i64 nw) {
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 w = (i64)blockIdx.x * blockDim.x + threadIdx.x; w < nw; w += stride) counts[w] = (u32)__popcll(keep_word(v, k, w, n));
-}
-void word_popcounts(hipStream_t s, const uint64_t *v, const uint64_t *k, int64_t n, uint32_t *counts, int64_t nw) {
-    if (nw <= 0) return;
-    hipLaunchKernelGGL(k_word_popcounts, dim3(grid_for(nw)), dim3(256), 0, s, (const u64 *)v, (const u64 *)k, (i64)n, counts, (i64)nw);
-}
-
-// exclusive scan of u32 counts in three passes: block sums (1024 per block), scan of the block sums by ONE
-// workgroup, per-block scan with offset.  Wave-level scans use DPP-free shuffles; 16 waves per block.
-__device__ __forceinline__ u32 wave_incl_scan(u32 x, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    return x;
-}
-__device__ __forceinline__ u32 block_excl_scan_1024(u32 x, u32 *lds, u32 &block_total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u32 incl = wave_incl_scan(x, lane);
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    if (wave == 0) {
-        const u32 t = lane < 16 ? lds[lane] : 0u;
-        const u32 ti = wave_incl_scan(t, lane);
-        if (lane < 16) lds[16 + lane] = ti - t;
-        if (lane == 15) lds[32] = ti;
-    }
-    __syncthreads();
-    block_total = lds[32];
-    const u32 r = lds[16 + wave] + incl - x;
-    __syncthreads();
-    return r;
-}
-__global__ void __launch_bounds__(1024) k_scan_block_sums(const u32 *in, u32 *block_sums, i64 n) {
-    __shared__ u32 lds[40];
-    const i64 i = (i64)blockIdx.x * 1024 + threadIdx.x;
-    u32 total;
-    (void)block_excl_scan_1024(i < n ? in[i] : 0u, lds, total);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-__global__ void __launch_bounds__(1024) k_scan_of_sums(u32 *block_sums, i64 nblocks, u64 *total_out) {
-    __shared__ u32 lds[40];
-    u64 carry = 0;
-    for (i64 base = 0; base < nblocks; base += 1024) {
-        const i64 i = base + threadIdx.x;
-        const u32 x = i < nblocks ? block_sums[i] : 0u;
-        u32 total;
-        const u32 e = block_excl_scan_1024(x, lds, total);
-        if (i < nblocks) block_sums[i] = (u32)(carry + e);
-        carry += total;
-    }
-    if (threadIdx.x == 0) *total_out = carry;
-}
-__global__ void __launch_bounds__(1024) k_scan_final(const u32 *in, const u32 *block_offsets, u32 *out, i64 n) {
-    __shared__ u32 lds[40];
-    const i64 i = (i64)blockIdx.x * 1024 + threadIdx.x;
-    u32 total;
-    const u32 e = block_excl_scan_1024(i < n ? in[i] : 0u, lds, total);
-    if (i < n) out[i] = block_offsets[blockIdx.x] + e;
-}
-void exclusive_scan_u32(hipStream_t s, const uint32_t *in, uint32_t *out, uint32_t *block_sums, int64_t n,
-                        unsigned long long *total) {
-    if (n <= 0) return;
-    const int64_t nblocks = (n + 1023) / 1024;
-    hipLaunchKernelGGL(k_scan_block_sums, dim3((unsigned)nblocks), dim3(1024), 0, s, in, block_sums, (i64)n);
-    hipLaunchKernelGGL(k_scan_of_sums, dim3(1), dim3(1024), 0, s, block_sums, (i64)nblocks, (u64 *)total);
-    hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nblocks), dim3(1024), 0, s, in, block_sums, out, (i64)n);
-}
-
-// A LANE per bitmap word: lane l walks the set bits of word w0 + l and writes their row ids from word_offsets[w] on.  The 64
-// words of a wave are adjacent and so are their output ranges, so step i of the walk is one store instruction with every
-// lane that still has a bit active, all within a few hundred bytes.  (One wave per word -- lanes = bits -- issued a store
-// instruction with ~3 active lanes per word at 5 % selectivity: 1.43 ms per 1 B rows.)
-// Round 2: when the wave's 64 words hold at most 1024 kept rows (the usual case below ~25 %) the row ids first meet in a 4 KiB
-// LDS buffer of the wave and leave in whole 256-byte store instructions: the direct form issues up to max-bits-per-word store
-// instructions of 64 lanes x 4 bytes spread over ~12 lines each (0.27 ms per 1 B rows at 10 %).
-__global__ void __launch_bounds__(256) k_expand_indices(const u64 *v, const u64 *k, i64 n, const u32 *word_offsets,
-                                                        u32 *indices, i64 nw) {
-    __shared__ u32 s_buf[4][1024];
-    u32 *buf = s_buf[threadIdx.x >> 6];
-    const int lane = threadIdx.x & 63;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    const i64 nw_pad = (nw + 63) & ~63ll;   // whole waves: the wave-level steps below need every lane
-    for (i64 w = (i64)blockIdx.x * blockDim.x + threadIdx.x; w < nw_pad; w += stride) {
-        u64 x = w < nw ? keep_word(v, k, w, n) : 0ull;
-        u32 pos = w < nw ? word_offsets[w] : 0u;
-        const u32 base = (u32)(w * 64);
-        const u32 first = (u32)__builtin_amdgcn_readfirstlane((int)pos);                                   // the wave's words are adjacent
-        const u32 cnt = (u32)__popcll(x);
-        // total of the wave: an inclusive scan is not needed, offsets are already exclusive -- last valid lane's pos + cnt
-        u32 endpos = pos + cnt;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const u32 t = (u32)__shfl_xor((int)endpos, o, 64);
-            endpos = t > endpos ? t : endpos;
-        }
-        const u32 total = endpos - first;
-        if (total <= 1024u) {
-            u32 q = pos - first;
-            while (x != 0) {
-                buf[q++] = base + (u32)__builtin_ctzll(x);
-                x &= x - 1;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            for (u32 j = (u32)lane; j < total; j += 64u) indices[first + j] = buf[j];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        } else {
-            while (x != 0) {
-                indices[pos++] = base + (u32)__builtin_ctzll(x);
-                x &= x - 1;
-            }
-        }
-    }
-}
-void expand_indices(hipStream_t s, const uint64_t *v, const uint64_t *k, int64_t n, const uint32_t *word_offsets,
-                    uint32_t *indices, int64_t nw) {
-    if (nw <= 0) return;
-    hipLaunchKernelGGL(k_expand_indices, dim3(grid_for(nw, 256, 256 * 8)), dim3(256), 0, s, (const u64 *)v, (const u64 *)k, (i64)n,
-                       word_offsets, indices, (i64)nw);
 }
 
 // Gather of up to 8 value columns at the kept row ids, one output row per lane and step, 4 rows in flight per lane: every

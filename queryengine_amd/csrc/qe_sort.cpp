@@ -5,7 +5,7 @@
 
 #include "qe_exec.h"
 #include "qe_kernels.h"
-#include "qe_pernode_kernels.h"
+#include "qe_scan.h"
 
 namespace qe {
 
@@ -136,10 +136,10 @@ void order_by_impl(qe_ctx *ctx, const qe_result *src, const qe_sort_key *keys, i
             }
             const int64_t nblocks = select_compact_blocks(n);
             uint32_t *counts = (uint32_t *)sc.alloc((size_t)nblocks * 4), *offsets = (uint32_t *)sc.alloc((size_t)nblocks * 4);
-            uint32_t *sums = (uint32_t *)sc.alloc((size_t)((nblocks + 1023) / 1024) * 4);
+            uint32_t *sums = (uint32_t *)sc.alloc((size_t)scan_blocks(nblocks) * 4);
             unsigned long long *d_total = (unsigned long long *)sc.alloc(16);
             launch_select_count(ctx->stream, img, n, st, counts);
-            pn::exclusive_scan_u32(ctx->stream, counts, offsets, sums, nblocks, d_total);
+            exclusive_scan<uint32_t>(ctx->stream, ArrayLoad<uint32_t>{counts}, offsets, sums, nblocks, d_total);
             unsigned long long c = 0;
             unsigned int passes = 0;
             QE_HIP(hipMemcpyAsync(&c, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));   // the one read-back of the selection

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "qe_kernels.h"
+#include "qe_scan.h"
 #include "qe_sort_image.h"
 
 namespace qe {
@@ -71,33 +72,6 @@ __global__ void __launch_bounds__(256) radix_hist_kernel(const u64 *keys, const 
     if (threadIdx.x < 16) hist[(i64)threadIdx.x * nblocks + blockIdx.x] = s_cnt[threadIdx.x];   // bucket-major: one scan gives the offsets
 }
 
-// exclusive scan of hist[16 * nblocks] by ONE workgroup (the table is small: 16 counters per 1024 rows)
-__global__ void __launch_bounds__(1024) radix_scan_kernel(u32 *hist, i64 total) {
-    __shared__ u32 s_wave[16];
-    __shared__ u32 s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (i64 b = 0; b < total; b += 1024) {
-        const i64 i = b + threadIdx.x;
-        const u32 v = i < total ? hist[i] : 0u;
-        u32 incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const u32 t = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += t;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        u32 before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < total) hist[i] = before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = before + incl;
-        __syncthreads();
-    }
-}
-
 // stable scatter: the block's 1024 elements in 4 rounds of 256 (index order); rank of an element = elements of its digit in
 // earlier rounds + in earlier waves of its round + in lower lanes of its wave (__ballot per digit, mbcnt)
 __global__ void __launch_bounds__(256) radix_scatter_kernel(const u64 *keys, const u32 *rows, const u64 *validity, i64 n, int shift, const u32 *offsets,
@@ -139,7 +113,7 @@ void launch_radix_pass(hipStream_t s, const unsigned long long *keys, const uint
     if (n <= 0) return;
     const i64 nblocks = (n + kSortBlock - 1) / kSortBlock;
     hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, (const u64 *)keys, rows, (const u64 *)validity, (i64)n, shift, hist, nblocks);
-    hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, s, hist, 16 * nblocks);
+    launch_carry_scan<u32, 1024>(s, hist, 16 * nblocks, 1, nullptr);   // the table is small: 16 counters per 1024 rows
     hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, (const u64 *)keys, rows, (const u64 *)validity, (i64)n, shift,
                        (const u32 *)hist, nblocks, (u64 *)keys_out, rows_out);
 }
@@ -214,12 +188,7 @@ __global__ void __launch_bounds__(64) select_step_kernel(SelectState *st, int sh
         st->hist[lane * 4 + j] = 0;   // ready for the next pass
         sum += c[j];
     }
-    u64 incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
+    const u64 incl = wave_incl_scan<u64>(sum, lane);
     const u64 rem = st->remaining;
     u64 cum = incl - sum;
     if (cum < rem && rem <= incl) {   // exactly one lane (1 <= rem <= rows that match the prefix)

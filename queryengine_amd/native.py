@@ -35,7 +35,9 @@ WIN_FIRST_VALUE, WIN_LAST_VALUE = 10, 11        # qe_result_window_frames only
 FRAME_UNBOUNDED = -1                             # QE_FRAME_UNBOUNDED: a frame edge at the partition's edge
 WIN_TILE_ROWS, WIN_TRIP_TILES = 2048, 1024   # the scan's tile and the tile aggregates one trip covers
 OSA_COUNT_DISTINCT, OSA_PERCENTILE_CONT, OSA_PERCENTILE_DISC, OSA_MODE = range(4)   # qe_result_group_ordered
-OSA_WORD_BLOCKS, OSA_BLOCKS = 128, 1024      # its grid caps in blocks of 256 lanes: a lane per bitmap word; a lane per group or run
+OSA_BLOCKS = 1024                            # its grid cap in blocks of 256 lanes: a lane per group or run
+OSA_WORD_BLOCKS = 128                        # 128 * 256 words = 2^21 rows: a size the ordered tests stay above (once a grid cap of its own
+                                             # lane-per-word kernels; those are the shared ones of DESIGN.md 3.11 now)
 
 
 class QeError(RuntimeError):

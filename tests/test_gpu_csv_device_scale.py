@@ -18,12 +18,14 @@ from queryengine_amd.csv_table import read_csv_device
 pytestmark = pytest.mark.gpu
 
 TILE = 4096                      # kTile: text bytes per wave of the structure passes
-SCAN_PER = 2048                  # kScanPer: elements per workgroup of scan_local_kernel
+SCAN_BLOCK = 1024                # kScanBlock (qe_scan.h): elements per workgroup of exclusive_scan, block sums per trip of its carry scan
+SCAN_PER = 2048                  # elements per workgroup of the parser's former recursive scan: its seams stay in the cases
 PACK_BLOCK = 256                 # distinct strings per block of dict_pack_kernel
 PATCH_CAP = 1 << 20              # undecided fields of one column that the patch list holds
-# scan() works on n + 1 elements (the total lands behind the last) in workgroups of kScanPer and scans the workgroup sums the
-# same way while there is more than one workgroup.  Up to 2047 workgroups their sums (+ 1) fit one workgroup: two levels.
-# The 2048th workgroup, and with it a third level, begins at n + 1 = 2047 * 2048 + 1.
+# scan() works on n + 1 elements (the total lands behind the last): exclusive_scan in workgroups of kScanBlock, whose sums ONE
+# workgroup scans in trips of kScanBlock with a carry.  Its second trip begins at n + 1 = 1024 * 1024 + 1.
+CARRY_TRIP = SCAN_BLOCK * SCAN_BLOCK
+# The former scan recursed instead: its 2048th workgroup, and with it a third level, began at n + 1 = 2047 * 2048 + 1.
 THREE_LEVEL = (SCAN_PER - 1) * SCAN_PER
 
 
@@ -102,10 +104,11 @@ def key_block():
     return rows, rows[::-1]
 
 
-@pytest.mark.parametrize("nrows", [THREE_LEVEL - 1, THREE_LEVEL, THREE_LEVEL + 2049])
+@pytest.mark.parametrize("nrows", [CARRY_TRIP - 2, CARRY_TRIP - 1, CARRY_TRIP + SCAN_BLOCK + 1, THREE_LEVEL - 1, THREE_LEVEL, THREE_LEVEL + 2049])
 def test_rank_scan_at_its_third_level(gpu_ctx, key_block, nrows):
-    """The rank scan of a STRING column runs over the rows: the only scan that can reach three levels (a tile scan would
-    need 16 GiB of text).  The last two-level row count, the first three-level one, and one a workgroup further."""
+    """The rank scan of a STRING column runs over the rows: the only scan of the parser that can reach the second trip of the
+    carry scan over the block sums (a tile scan would need 4 GiB of text).  The scanned n + 1 elements are one short of a full
+    trip, exactly one trip, and one block past it; then the row counts at which the former recursive scan took its third level."""
     rows, other = key_block
     # NULLs in the last 64-row word: of the key, of the flag, of both
     last = [",true\n", "7,\n", ",\n", "a,false\n"] * 16
@@ -127,10 +130,11 @@ def dict_text(rng, strings, copies=3, empty=0.05):
 KV = Schema([Field("k", S), Field("v", D)])
 
 
-@pytest.mark.parametrize("nd", [PACK_BLOCK - 1, PACK_BLOCK, PACK_BLOCK + 1, SCAN_PER - 1, SCAN_PER, SCAN_PER + 1, 5003])
+@pytest.mark.parametrize("nd", [PACK_BLOCK - 1, PACK_BLOCK, PACK_BLOCK + 1, SCAN_BLOCK - 1, SCAN_BLOCK, SCAN_BLOCK + 1, SCAN_PER - 1, SCAN_PER, SCAN_PER + 1,
+                                5003])
 def test_dictionary_sizes(gpu_ctx, nd):
     """nd distinct strings: dict_pack_kernel's second block begins at 257, and the scan over their nd + 1 lengths takes a
-    second workgroup from nd = 2048 on.  Every string appears three times in shuffled order, so the order of first appearance
+    second workgroup from nd = 1024 on (from 2048 on in the former scan).  Every string appears three times in shuffled order, so the order of first appearance
     is neither the sorted order nor the order of the hash table."""
     rng = random.Random(nd)
     strings = [f"k{i}" + "é" * (i % 3) + "x" * (i * 7 % 37) for i in range(nd)]
@@ -230,9 +234,9 @@ def tile_lengths(ntiles):
     return [(ntiles - 1) * TILE + 1, ntiles * TILE - 1, ntiles * TILE]
 
 
-@pytest.mark.parametrize("ntiles", [1, 2, 3, SCAN_PER - 1, SCAN_PER, SCAN_PER + 1])
+@pytest.mark.parametrize("ntiles", [1, 2, 3, SCAN_BLOCK - 1, SCAN_BLOCK, SCAN_BLOCK + 1, SCAN_PER - 1, SCAN_PER, SCAN_PER + 1])
 def test_tile_counts_lengths_and_last_bytes(gpu_ctx, ntiles):
-    """2047 tiles (+ 1 for the total) are the last that one workgroup of the tile scans holds.  At a length of 0 or 1 mod 4096
+    """1023 tiles (+ 1 for the total) are the last that one workgroup of the tile scans holds (2047 in the former scan).  At a length of 0 or 1 mod 4096
     the text's last byte is the last or the only byte of its tile, and when that byte is a closing quote, a lone \\r or the \\n
     of a \\r\\n, the end-of-text and carried-byte branches of records_kernel decide alone."""
     for n in tile_lengths(ntiles) if ntiles > 1 else [TILE - 1, TILE]:   # (no ending fits a body of one byte)

@@ -21,10 +21,10 @@ pytestmark = pytest.mark.gpu
 D, I64, I32, B, S = DataType.DOUBLE, DataType.INT64, DataType.INT32, DataType.BOOLEAN, DataType.STRING
 TAGS = ["t0", "", "täg", "t3", "t4"]
 PROBE_BLOCK = 256                # rows per block of join_count_kernel / join_write_kernel
-SCAN_WIDTH = 1024                # block sums per trip of join_scan_kernel
+SCAN_WIDTH = 1024                # block sums per trip of the join's launch_carry_scan<u64, 1024>
 ROW_GRID = 8192 * 256            # threads of the capped grids of join_build_keys_kernel, join_directory_kernel, gather_rows_kernel
 GATHER_GRID = 16384 * 256        # ... of gather_rows_kernel and gather_bits_rows_kernel as the join launches them for its output columns
-RADIX_SCAN_WIDTH = 1024          # counters per trip of radix_scan_kernel: 16 per 1024 rows
+RADIX_SCAN_WIDTH = 1024          # counters per trip of the radix pass's launch_carry_scan<u32, 1024>: 16 per 1024 rows
 
 
 def payload(rng, n, specials=True):
@@ -131,7 +131,7 @@ DIR_BITS = {16: 4, 17: 5, 32: 5, 33: 6, 100: 7, 256: 8, 257: 9, 2_000: 11, 4_096
 @pytest.mark.parametrize("m", sorted(DIR_BITS))
 def test_directory_of_every_width_mod_4_and_both_sides_of_a_power_of_two(gpu_ctx, m):
     """dbits = the first width with 2^dbits >= keyed rows (at least 4); the sort covers ceil(dbits / 4) digits, so dbits mod 4
-    says how many hash bits below the bucket bits are sorted.  65 537 rows also take radix_scan_kernel past one trip."""
+    says how many hash bits below the bucket bits are sorted.  65 537 rows also take the radix pass's carry scan past one trip."""
     dbits = 4
     while (1 << dbits) < m:
         dbits += 1
@@ -171,7 +171,7 @@ def test_directory_of_every_width_mod_4_and_both_sides_of_a_power_of_two(gpu_ctx
 def test_build_side_past_the_grid_cap(gpu_ctx, null_share):
     """2 097 152 + 321 build rows: join_build_keys_kernel strides; more than 2^20 keyed rows: dbits >= 21, so
     join_directory_kernel strides over 2^21 + 1 entries; 3 % NULL keys: the pass that moves keyless rows behind the others
-    (and radix_scan_kernel's carry) at that size.  Without NULL keys every row is keyed: gather_rows_kernel<u64> strides
+    (and the carry of the radix pass's scan) at that size.  Without NULL keys every row is keyed: gather_rows_kernel<u64> strides
     over the table's key images."""
     nb = ROW_GRID + 321
     rng = np.random.default_rng(63)

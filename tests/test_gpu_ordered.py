@@ -4,8 +4,8 @@ The expectation is tests/ordered_reference.py (numpy; proved equal to the host b
 tests/test_ordered_cpu.py).  Every output column is compared in full -- type, nullability, dictionary, validity, values by
 bits, PERCENTILE_CONT included (the comparison takes any NaN for any NaN: the header leaves a NaN's payload to the formula) --
 and the value under every NULL must be zero.  There is no tolerance anywhere.  Sizes are those where the kernels change
-behaviour: word (64) and tile (2048) edges of the bitmaps, one trip of the tile-count scan (native.WIN_TRIP_TILES tiles), and
-the two grid caps native.OSA_WORD_BLOCKS (a lane per bitmap word) and native.OSA_BLOCKS (a lane per group or run).
+behaviour: word (64) and tile (2048) edges of the bitmaps, more than one 1024-word block of the word-rank scan (the shared
+scan's own trips and sweeps are tested at their seams in tests/scan), and the grid cap native.OSA_BLOCKS (a lane per group or run).
 
 One error of the contract has no test: a STRING column without a dictionary cannot be built through the ABI."""
 import ctypes as C
@@ -30,9 +30,9 @@ FRACTIONS = [0.0, 0.25, 1 / 3, 0.5, 2 / 3, 0.999, 1.0]
 STRINGS = ["b", "a", "", "B", "～", "\U0001F600", "aa", "Zü", "zz", "a "]     # not in sorted order
 SEAM_N = 3 * T + 37
 SEAM_LENGTHS = [1, 2, 63, 64, 65, 512, 513, 2048, 2049]
-BIG = TRIP * T + 321            # one trip of the tile-count scan and a ragged tail; also past OSA_WORD_BLOCKS * 256 words
+BIG = TRIP * T + 321            # 32 blocks of the word-rank scan and a ragged tail; also past OSA_WORD_BLOCKS * 256 words
 GROUP_CAP = N.OSA_BLOCKS * 256  # lanes of one sweep of the per-group and per-run kernels
-assert BIG > N.OSA_WORD_BLOCKS * 256 * 64
+assert BIG > N.OSA_WORD_BLOCKS * 256 * 64 and BIG // 64 > 1024
 
 
 def build(ctx, cols):
