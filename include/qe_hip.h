@@ -67,11 +67,18 @@ enum {
  */
 enum { QE_OP_COLUMN = 1, QE_OP_NUM_LITERAL = 2, QE_OP_BOOL_LITERAL = 3, QE_OP_STR_LITERAL = 4, QE_OP_FUNCTION = 16 };
 
-/* ast/Functions.kt:7-22 ordinals */
+/* Ordinals 0-16 are the reference's (ast/Functions.kt:7-22).  Ordinals 17-22 are extensions the reference's
+ * enum does not have (additive: header version and ABI version stay 1):
+ *   IS_NULL / IS_NOT_NULL  1 operand of any type -> BOOLEAN, never NULL: the validity of the operand EXPRESSION
+ *   COALESCE               2 operands typed like the branches of IF -> a where a is valid, else b (NULL iff both are)
+ *   ABS                    numeric -> operand type; Math.abs (-0.0 -> 0.0, NaN stays NaN, MIN_VALUE stays MIN_VALUE)
+ *   FLOOR / CEIL           numeric -> operand type; Math.floor / Math.ceil on DOUBLE, the identity on integers
+ * ABS, FLOOR and CEIL map NULL to NULL. */
 enum {
     QE_FN_AND = 0, QE_FN_OR, QE_FN_IF, QE_FN_NOT, QE_FN_UNARY_MINUS, QE_FN_UNARY_PLUS, QE_FN_MUL, QE_FN_DIV,
     QE_FN_MOD, QE_FN_ADD, QE_FN_SUB, QE_FN_CMP_LT, QE_FN_CMP_LE, QE_FN_CMP_GE, QE_FN_CMP_GT, QE_FN_CMP_EQ,
-    QE_FN_CMP_NE, QE_FN_COUNT_
+    QE_FN_CMP_NE,
+    QE_FN_IS_NULL = 17, QE_FN_IS_NOT_NULL, QE_FN_COALESCE, QE_FN_ABS, QE_FN_FLOOR, QE_FN_CEIL, QE_FN_COUNT_
 };
 
 /* ast/Functions.kt:24-26 ordinals (ANY/ALL are TODO() in the reference: Accumulators.kt:16-17) */

@@ -1,9 +1,9 @@
 """Expression tree: the input language of the hot path.
 
 Mirrors ``ast/Expressions.kt:6-62`` (node classes), ``ast/Functions.kt:3-26``
-(``FunctionType``, ``Function`` with type and arity; ordinals identical to the
+(``FunctionType``, ``Function`` with type and arity; ordinals 0-16 identical to the
 Kotlin enum so that the serialised program is what a Kotlin-side serialiser
-would emit from ``Function.ordinal``) and ``ast/ExpressionVisitor.kt:3-13``.
+would emit from ``Function.ordinal``; 17-22 are extensions the enum does not have) and ``ast/ExpressionVisitor.kt:3-13``.
 """
 from __future__ import annotations
 
@@ -41,6 +41,17 @@ class Function(enum.Enum):
     CMP_GT = (14, FunctionType.COMPARISON, 2)
     CMP_EQ = (15, FunctionType.COMPARISON, 2)
     CMP_NE = (16, FunctionType.COMPARISON, 2)
+    # extensions: not in the Kotlin enum (QE_FN_* 17-22 of include/qe_hip.h)
+    IS_NULL = (17, FunctionType.LOGIC, 1)        # extension
+    IS_NOT_NULL = (18, FunctionType.LOGIC, 1)    # extension
+    COALESCE = (19, FunctionType.LOGIC, 2)       # extension
+    ABS = (20, FunctionType.ARITHMETIC, 1)       # extension
+    FLOOR = (21, FunctionType.ARITHMETIC, 1)     # extension
+    CEIL = (22, FunctionType.ARITHMETIC, 1)      # extension
+
+    @property
+    def is_extension(self) -> bool:
+        return self.ordinal > 16
 
     @property
     def ordinal(self) -> int:

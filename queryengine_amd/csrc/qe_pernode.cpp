@@ -243,6 +243,58 @@ struct Exec {
         return eval(e, oid);
     }
 
+    // STRING values of two branches (IF's THEN / ELSE, COALESCE's operands) in ONE dictionary; the codes of a non-literal first
+    // side stay valid (its dictionary is a prefix of the union), the second side's codes are remapped (lookup_codes) when its
+    // dictionary is another one, literals become codes (appended when absent)
+    std::shared_ptr<DictData> unify_dictionaries(Vec &t, Vec &f) {
+        auto ndct = std::make_shared<DictData>();
+        const Vec *base = !t.is_str_lit ? &t : (!f.is_str_lit ? &f : nullptr);
+        if (base) { *ndct = *base->dict; ndct->id = DictData::next_id(); }
+        if (!t.is_str_lit && !f.is_str_lit && t.dict != f.dict) {
+            // union dictionary: the first side's dictionary is its prefix, the second side's codes are remapped
+            std::vector<int32_t> fmap;
+            for (const std::string &str : f.dict->entries) {
+                int32_t code = ndct->find(str);
+                if (code < 0) {
+                    code = (int32_t)ndct->entries.size();
+                    ndct->entries.push_back(str);
+                    ndct->index[str] = code;
+                }
+                fmap.push_back(code);
+            }
+            f.data = lookup(fmap, f);
+        }
+        auto resolve = [&](Vec &x) {
+            if (!x.is_str_lit) return;
+            int32_t code = ndct->find(x.lit);
+            if (code < 0) {
+                code = (int32_t)ndct->entries.size();
+                ndct->entries.push_back(x.lit);
+                ndct->index[x.lit] = code;
+            }
+            x.i = code;
+            x.is_str_lit = false;
+        };
+        resolve(t);
+        resolve(f);
+        return ndct;
+    }
+
+    // validity words of node `oid` in the current domain (null: it cannot be NULL) WITHOUT its values: a batch column in a
+    // narrowed domain has only its bitmap gathered
+    Buf validity(const Expr &e, int oid) {
+        const Node &on = e.nodes[oid];
+        if (on.kind == N_COLUMN && on.col >= 0 && on.col < (int)base.size() && base[(size_t)on.col].type == on.type) {
+            const Vec &b = base[(size_t)on.col];
+            if (!ids || !b.valid) return b.valid;
+            if (env[(size_t)on.col].data) return env[(size_t)on.col].valid;
+            Buf k = alloc_words();
+            launch_gather_bits_rows(s, (const uint64_t *)b.valid.get(), (const uint32_t *)ids.get(), n, (uint64_t *)k.get());
+            return k;
+        }
+        return eval(e, oid).valid;
+    }
+
     Vec eval(const Expr &e, int id) {
         const Node &nd = e.nodes[id];
         Vec r;
@@ -400,38 +452,7 @@ struct Exec {
             Buf cond = c.data;
             if (c.valid) cond = and_valid(c.data, c.valid);   // c = vc & kc
             if (nd.type == QE_STRING) {
-                // unify dictionaries; the codes of a non-literal side stay valid (its dictionary is a prefix)
-                auto ndct = std::make_shared<DictData>();
-                const Vec *base = !t.is_str_lit ? &t : (!f.is_str_lit ? &f : nullptr);
-                if (base) { *ndct = *base->dict; ndct->id = DictData::next_id(); }
-                if (!t.is_str_lit && !f.is_str_lit && t.dict != f.dict) {
-                    // union dictionary: THEN side's dictionary is its prefix, the ELSE side's codes are remapped
-                    std::vector<int32_t> fmap;
-                    for (const std::string &str : f.dict->entries) {
-                        int32_t code = ndct->find(str);
-                        if (code < 0) {
-                            code = (int32_t)ndct->entries.size();
-                            ndct->entries.push_back(str);
-                            ndct->index[str] = code;
-                        }
-                        fmap.push_back(code);
-                    }
-                    f.data = lookup(fmap, f);
-                }
-                auto resolve = [&](Vec &x) {
-                    if (!x.is_str_lit) return;
-                    int32_t code = ndct->find(x.lit);
-                    if (code < 0) {
-                        code = (int32_t)ndct->entries.size();
-                        ndct->entries.push_back(x.lit);
-                        ndct->index[x.lit] = code;
-                    }
-                    x.i = code;
-                    x.is_str_lit = false;
-                };
-                resolve(t);
-                resolve(f);
-                r.dict = ndct;
+                r.dict = unify_dictionaries(t, f);
             }
             if (nd.type == QE_BOOLEAN) {
                 Vec tt = materialize(t), ff = materialize(f);
@@ -453,14 +474,57 @@ struct Exec {
             }
             return r;
         }
+        case QE_FN_IS_NULL: case QE_FN_IS_NOT_NULL: {   // word operations on the operand's validity; its data is never read
+            const Buf k = validity(e, nd.ops[0]);
+            const bool is_null = nd.fn == QE_FN_IS_NULL;
+            r.data = alloc_words();
+            if (!k) pn::word_fill(s, is_null ? 0ull : ~0ull, (uint64_t *)r.data.get(), bitmap_words(n));
+            else if (is_null) pn::word_not(s, (const uint64_t *)k.get(), (uint64_t *)r.data.get(), bitmap_words(n));
+            else if (n > 0) QE_HIP(hipMemcpyAsync(r.data.get(), k.get(), bitmap_bytes(n), hipMemcpyDeviceToDevice, s));
+            return r;
+        }
+        case QE_FN_COALESCE: {   // select on the first operand's validity words; NULL iff both operands are
+            Vec a = eval(e, nd.ops[0]), b = eval(e, nd.ops[1]);
+            if (!a.valid) return a;   // never NULL: the node is its first operand
+            if (nd.type == QE_STRING) r.dict = unify_dictionaries(a, b);
+            if (nd.type == QE_BOOLEAN) {
+                Vec bb = materialize(b);
+                r.data = alloc_words();
+                pn::select_words(s, (const uint64_t *)a.valid.get(), (const uint64_t *)a.data.get(), (const uint64_t *)bb.data.get(),
+                                 (uint64_t *)r.data.get(), bitmap_words(n));
+            } else {
+                r.data = alloc_col(nd.type);
+                pn::select(s, kernel_type(nd.type), (const uint64_t *)a.valid.get(), opnd(a), opnd(b), r.data.get(), n);
+            }
+            if (b.valid) {
+                r.valid = alloc_words();
+                pn::word_op(s, pn::W_OR, (const uint64_t *)a.valid.get(), (const uint64_t *)b.valid.get(), (uint64_t *)r.valid.get(), bitmap_words(n));
+            }
+            return r;
+        }
+        case QE_FN_ABS: case QE_FN_FLOOR: case QE_FN_CEIL: {
+            Vec a = eval(e, nd.ops[0]);
+            if (nd.fn != QE_FN_ABS && nd.type != QE_DOUBLE) return a;   // an integer is its own floor and ceiling
+            a = materialize(a);
+            r.valid = a.valid;
+            r.data = alloc_col(nd.type);
+            pn::unary(s, nd.type, nd.fn == QE_FN_ABS ? pn::U_ABS : nd.fn == QE_FN_FLOOR ? pn::U_FLOOR : pn::U_CEIL, a.data.get(), r.data.get(), n);
+            return r;
+        }
         default: fail(QE_ERR_INTERNAL, "bad function");
         }
     }
 };
 
 void collect_columns(const Expr &e, std::vector<char> &used) {
+    // (the direct operand of a null test is asked for its validity words only: Exec::validity)
+    std::vector<char> null_tested(e.nodes.size(), 0);
     for (const Node &nd : e.nodes)
-        if (nd.kind == N_COLUMN && nd.col >= 0 && nd.col < (int)used.size()) used[nd.col] = 1;
+        if (nd.kind == N_FN && (nd.fn == QE_FN_IS_NULL || nd.fn == QE_FN_IS_NOT_NULL)) null_tested[(size_t)nd.ops[0]] = 1;
+    for (size_t id = 0; id < e.nodes.size(); id++) {
+        const Node &nd = e.nodes[id];
+        if (nd.kind == N_COLUMN && !null_tested[id] && nd.col >= 0 && nd.col < (int)used.size()) used[nd.col] = 1;
+    }
 }
 
 }  // namespace

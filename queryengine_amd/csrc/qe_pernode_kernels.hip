@@ -1,5 +1,5 @@
 // qe_pernode_kernels.hip -- one precompiled gfx950 kernel per expression node kind
-// (SURVEY 2.1 kernel inventory): arithmetic, negate, cast, comparison -> bitmap via
+// (SURVEY 2.1 kernel inventory): arithmetic, negate, ABS / FLOOR / CEIL, cast, comparison -> bitmap via
 // __ballot, Kleene logic on 64-row words, IF select, and the gather behind the
 // filter's stable compaction (bitmap_ranks -> bitmap_positions of qe_scan.h -> gather).
 //
@@ -153,6 +153,42 @@ void negate(hipStream_t s, int type, const void *a, void *out, int64_t n) {
     if (type == QE_DOUBLE) hipLaunchKernelGGL(k_neg<double>, dim3(g), dim3(256), 0, s, (const double *)a, (double *)out, (i64)n);
     else if (type == QE_INT64) hipLaunchKernelGGL(k_neg<i64>, dim3(g), dim3(256), 0, s, (const i64 *)a, (i64 *)out, (i64)n);
     else hipLaunchKernelGGL(k_neg<int>, dim3(g), dim3(256), 0, s, (const int *)a, (int *)out, (i64)n);
+}
+
+// ABS / FLOOR / CEIL (extensions): Math.abs clears the sign bit (-0.0 -> 0.0, NaN stays NaN) and wraps at long / int MIN_VALUE;
+// Math.floor / Math.ceil are the IEEE roundings (ceil(-0.5) = -0.0).  The executor never launches FLOOR / CEIL on integers.
+template <typename T, int OP> struct UnaryOp;
+template <int OP> struct UnaryOp<double, OP> {
+    static __device__ __forceinline__ double apply(double a) {
+        if (OP == U_ABS) return __builtin_fabs(a);
+        if (OP == U_FLOOR) return floor(a);
+        return ceil(a);
+    }
+};
+template <int OP> struct UnaryOp<i64, OP> {
+    static __device__ __forceinline__ i64 apply(i64 a) { return OP == U_ABS && a < 0 ? (i64)(0ull - (u64)a) : a; }
+};
+template <int OP> struct UnaryOp<int, OP> {
+    static __device__ __forceinline__ int apply(int a) { return OP == U_ABS && a < 0 ? (int)(0u - (u32)a) : a; }
+};
+template <typename T, int OP>
+__global__ void __launch_bounds__(256) k_unary(const T *a, T *out, i64 n) {
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = UnaryOp<T, OP>::apply(a[i]);
+}
+template <typename T> static void unary_t(hipStream_t s, int op, const void *a, void *out, int64_t n) {
+    const int g = grid_for(n);
+    switch (op) {
+    case U_ABS: hipLaunchKernelGGL((k_unary<T, U_ABS>), dim3(g), dim3(256), 0, s, (const T *)a, (T *)out, (i64)n); break;
+    case U_FLOOR: hipLaunchKernelGGL((k_unary<T, U_FLOOR>), dim3(g), dim3(256), 0, s, (const T *)a, (T *)out, (i64)n); break;
+    default: hipLaunchKernelGGL((k_unary<T, U_CEIL>), dim3(g), dim3(256), 0, s, (const T *)a, (T *)out, (i64)n); break;
+    }
+}
+void unary(hipStream_t s, int type, int op, const void *a, void *out, int64_t n) {
+    if (n <= 0) return;
+    if (type == QE_DOUBLE) unary_t<double>(s, op, a, out, n);
+    else if (type == QE_INT64) unary_t<i64>(s, op, a, out, n);
+    else unary_t<int>(s, op, a, out, n);
 }
 
 template <typename F, typename T>

@@ -5,7 +5,7 @@
 // reference's own (host/test_host.cpp follows T/evaluator/CompilerTest.kt).
 //
 //   ast/Expressions.kt:6-62      -> Expression, *LiteralExpression, ColumnExpression, FunctionExpression
-//   ast/Functions.kt:7-22        -> Function (ordinals identical)
+//   ast/Functions.kt:7-22        -> Function (ordinals identical; 17-22 are extensions)
 //   data/Schema.kt:3-13          -> DataType (+INT64, INT32), Field, Schema
 //   data/MemoryTable.kt:7-19     -> ColumnarTable (the columnar scan leaf)
 //   operator/Operators.kt:5-32   -> Operator, forEach, map
@@ -31,7 +31,11 @@ namespace queryengine {
 enum class DataType { STRING = 0, DOUBLE = 1, BOOLEAN = 2, INT64 = 3, INT32 = 4 };
 
 enum class Function {
-    AND = 0, OR, IF, NOT, UNARY_MINUS, UNARY_PLUS, MUL, DIV, MOD, ADD, SUB, CMP_LT, CMP_LE, CMP_GE, CMP_GT, CMP_EQ, CMP_NE
+    AND = 0, OR, IF, NOT, UNARY_MINUS, UNARY_PLUS, MUL, DIV, MOD, ADD, SUB, CMP_LT, CMP_LE, CMP_GE, CMP_GT, CMP_EQ, CMP_NE,
+    // extensions (not in ast/Functions.kt; QE_FN_* 17-22).  FunctionExpression serialises the ordinal and leaves the result
+    // type to the library (0xFF), which infers it: BOOLEAN for the null tests, the IF rule for COALESCE, the operand's type
+    // for ABS / FLOOR / CEIL
+    IS_NULL = 17, IS_NOT_NULL, COALESCE, ABS, FLOOR, CEIL
 };
 
 enum class Mode { GPU_FUSED, GPU_PER_NODE };

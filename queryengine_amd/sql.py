@@ -7,9 +7,10 @@ available here, and the parser is host-side planning outside the hot path
 SQL text in tests and in bench.py.  It keeps the grammar's precedence, which
 follows the order of the alternatives of ``expression`` (Query.g4:27-40):
 
-    unary (- + NOT)  >  * / %  >  + -  >  comparison  >  AND  >  OR
+    unary (- + NOT)  >  * / %  >  + -  >  comparison, IS [NOT] NULL  >  AND  >  OR
 
-(note that NOT binds tighter than comparison, as in the reference), all binary
+(note that NOT binds tighter than comparison, as in the reference: ``NOT c IS NULL`` is ``(NOT c) IS NULL``;
+the postfix null tests and n-ary ``COALESCE(a, b, c)`` = ``COALESCE(a, COALESCE(b, c))`` are extensions), all binary
 operators left-associative, case-insensitive keywords, numeric literals always
 DOUBLE, unary minus/plus folded into numeric literals
 (ExpressionAstBuilder.kt:104-110).
@@ -117,10 +118,21 @@ class _Parser:
 
     def compare(self):
         left = self.add()
-        while self.peek()[0] == "op" and self.peek()[1] in _COMPARISONS:
-            op = self.take()[1]
-            left = FunctionExpression(_COMPARISONS[op], [left, self.add()])
-        return left
+        while True:
+            k, v = self.peek()
+            if k == "op" and v in _COMPARISONS:
+                self.take()
+                left = FunctionExpression(_COMPARISONS[v], [left, self.add()])
+            elif k == "ident" and v.upper() == "IS":
+                # postfix x IS [NOT] NULL (an extension; IS and NULL stay plain identifiers everywhere else)
+                self.take()
+                negated = self.accept("kw", "NOT")
+                k, v = self.take()
+                if k != "ident" or v.upper() != "NULL":
+                    raise SyntaxException(f"expected NULL but found '{v}'")
+                left = FunctionExpression(Function.IS_NOT_NULL if negated else Function.IS_NULL, [left])
+            else:
+                return left
 
     def add(self):
         left = self.mul()
@@ -175,6 +187,11 @@ class _Parser:
                     ops.append(self.expression())
                 self.expect("op", ")")
                 name = v.upper()
+                if name == "COALESCE" and len(ops) > 2:                 # n-ary: folds to the right
+                    e = ops[-1]
+                    for op in reversed(ops[:-1]):
+                        e = FunctionExpression(Function.COALESCE, [op, e])
+                    return e
                 if name in Function.__members__:
                     return FunctionExpression(Function[name], ops)
                 if name in AggregationFunction.__members__:

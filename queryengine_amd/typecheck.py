@@ -1,11 +1,13 @@
 """Type assignment for function nodes -- the host-side twin of the checks libqe_hip repeats
 when it verifies a program.
 
-Follows ``evaluator/TypeCheck.kt:38-133`` with three deliberate differences:
+Follows ``evaluator/TypeCheck.kt:38-133`` with four deliberate differences:
   * AND/OR require BOTH operands BOOLEAN (TypeCheck.kt:79-85 demands operands[0] == DOUBLE: a bug
     that makes every ``p AND q`` fail);
   * unary operators check one operand (TypeCheck.kt:50-52 indexes operands[1]);
-  * numeric = {DOUBLE, INT64, INT32} with Java binary numeric promotion (extension types).
+  * numeric = {DOUBLE, INT64, INT32} with Java binary numeric promotion (extension types);
+  * the extension functions IS_NULL / IS_NOT_NULL (any type -> BOOLEAN), COALESCE (typed as IF's branches) and
+    ABS / FLOOR / CEIL (numeric -> the operand's type).
 """
 from __future__ import annotations
 
@@ -29,7 +31,7 @@ class _TypeCheckVisitor(DefaultExpressionVisitor):
         if len(ops) != f.arity:
             raise TypeCheckException(f"[{f.name}] expects {f.arity} operands, got {len(ops)}")
         B = DataType.BOOLEAN
-        if f in (Function.UNARY_MINUS, Function.UNARY_PLUS):
+        if f in (Function.UNARY_MINUS, Function.UNARY_PLUS, Function.ABS, Function.FLOOR, Function.CEIL):
             if not ops[0].dataType.is_numeric:
                 raise _invalid(f, ops)
             return expr.with_(ops, ops[0].dataType)
@@ -62,6 +64,15 @@ class _TypeCheckVisitor(DefaultExpressionVisitor):
                 if ops[1].dataType != ops[2].dataType:
                     raise _invalid(f, ops)
                 t = ops[1].dataType
+            return expr.with_(ops, t)
+        if f in (Function.IS_NULL, Function.IS_NOT_NULL):   # any operand type; never NULL itself
+            return expr.with_(ops, B)
+        if f == Function.COALESCE:                           # typed as the two branches of IF
+            t = promote(ops[0].dataType, ops[1].dataType)
+            if t is None:
+                if ops[0].dataType != ops[1].dataType:
+                    raise _invalid(f, ops)
+                t = ops[0].dataType
             return expr.with_(ops, t)
         raise TypeCheckException(f"unknown function {f}")
 
