@@ -4,9 +4,8 @@
 // node of the typed tree becomes one launch of a precompiled kernel (qe_pernode_kernels.hip) over
 // whole columns; BOOLEAN values and validity travel as 64-row bitmap words.  The executor is
 // filter-first, conjunct by conjunct (late materialisation at node granularity):
-//   1. the Filter's top-level AND chain is split into its conjuncts (FilterOperator keeps a row iff the predicate is a
-//      non-null TRUE, FilterOperator.kt:20, and a Kleene AND is TRUE iff every operand is: the keep mask of the chain is the
-//      AND of the conjuncts' keep masks; the reference's AND is lazy in the same direction, Interpreter.kt:54-72)
+//   1. the Filter's top-level AND chain is split into its conjuncts (split_conjuncts; the reference's AND is lazy in the same
+//      direction, Interpreter.kt:54-72)
 //   2. a conjunct is evaluated over the CURRENT domain -> keep = value & known -> word popcounts -> scan; when at most half
 //      of the domain survives (or it is the last conjunct) the domain is narrowed to the kept rows: ascending row ids,
 //      columns already gathered are re-gathered from their compact copies
@@ -18,10 +17,9 @@
 
 #include <cstdlib>
 #include <algorithm>
-#include <cmath>
-#include <functional>
 
 #include "qe_exec.h"
+#include "qe_expr_rules.h"
 #include "qe_kernels.h"
 #include "qe_pernode_kernels.h"
 #include "qe_scan.h"
@@ -234,8 +232,7 @@ struct Exec {
     // itself plus the domain's row ids (a selection vector) when the domain is narrowed and holds no copy of it
     Vec operand(const Expr &e, int oid) {
         const Node &on = e.nodes[oid];
-        if (on.kind == N_COLUMN && ids && on.col >= 0 && on.col < (int)through_ids.size() && through_ids[(size_t)on.col] &&
-            !env[(size_t)on.col].data && base[(size_t)on.col].type == on.type) {
+        if (on.kind == N_COLUMN && ids && through_ids[(size_t)on.col] && !env[(size_t)on.col].data) {
             Vec v = base[(size_t)on.col];   // non-owning: read as column[ids[j]]
             v.indexed = true;
             return v;
@@ -243,48 +240,22 @@ struct Exec {
         return eval(e, oid);
     }
 
-    // STRING values of two branches (IF's THEN / ELSE, COALESCE's operands) in ONE dictionary; the codes of a non-literal first
-    // side stay valid (its dictionary is a prefix of the union), the second side's codes are remapped (lookup_codes) when its
-    // dictionary is another one, literals become codes (appended when absent)
-    std::shared_ptr<DictData> unify_dictionaries(Vec &t, Vec &f) {
-        auto ndct = std::make_shared<DictData>();
-        const Vec *base = !t.is_str_lit ? &t : (!f.is_str_lit ? &f : nullptr);
-        if (base) { *ndct = *base->dict; ndct->id = DictData::next_id(); }
-        if (!t.is_str_lit && !f.is_str_lit && t.dict != f.dict) {
-            // union dictionary: the first side's dictionary is its prefix, the second side's codes are remapped
-            std::vector<int32_t> fmap;
-            for (const std::string &str : f.dict->entries) {
-                int32_t code = ndct->find(str);
-                if (code < 0) {
-                    code = (int32_t)ndct->entries.size();
-                    ndct->entries.push_back(str);
-                    ndct->index[str] = code;
-                }
-                fmap.push_back(code);
-            }
-            f.data = lookup(fmap, f);
-        }
-        auto resolve = [&](Vec &x) {
-            if (!x.is_str_lit) return;
-            int32_t code = ndct->find(x.lit);
-            if (code < 0) {
-                code = (int32_t)ndct->entries.size();
-                ndct->entries.push_back(x.lit);
-                ndct->index[x.lit] = code;
-            }
-            x.i = code;
-            x.is_str_lit = false;
-        };
-        resolve(t);
-        resolve(f);
-        return ndct;
+    static StrSide side(const Vec &x) { return x.is_str_lit ? StrSide{nullptr, &x.lit} : StrSide{x.dict.get(), nullptr}; }
+
+    // carries unify_dictionaries out: literals become their codes, the second side's codes are remapped (lookup_codes) where it says so
+    std::shared_ptr<DictData> unify(Vec &t, Vec &f) {
+        const DictUnion u = unify_dictionaries(side(t), side(f));
+        if (u.remap_second) f.data = lookup(u.remap, f);
+        if (t.is_str_lit) { t.i = u.lit[0]; t.is_str_lit = false; }
+        if (f.is_str_lit) { f.i = u.lit[1]; f.is_str_lit = false; }
+        return u.dict;
     }
 
     // validity words of node `oid` in the current domain (null: it cannot be NULL) WITHOUT its values: a batch column in a
     // narrowed domain has only its bitmap gathered
     Buf validity(const Expr &e, int oid) {
         const Node &on = e.nodes[oid];
-        if (on.kind == N_COLUMN && on.col >= 0 && on.col < (int)base.size() && base[(size_t)on.col].type == on.type) {
+        if (on.kind == N_COLUMN) {
             const Vec &b = base[(size_t)on.col];
             if (!ids || !b.valid) return b.valid;
             if (env[(size_t)on.col].data) return env[(size_t)on.col].valid;
@@ -300,13 +271,7 @@ struct Exec {
         Vec r;
         r.type = nd.type;
         switch (nd.kind) {
-        case N_COLUMN: {
-            if (nd.col < 0 || nd.col >= (int)base.size()) fail(QE_ERR_PROGRAM, "column index out of range");
-            if (base[nd.col].type != nd.type)
-                fail(QE_ERR_PROGRAM, std::string("column ") + std::to_string(nd.col) + " is " + type_name(base[nd.col].type) +
-                                         " in the batch but " + type_name(nd.type) + " in the expression");
-            return column(nd.col);
-        }
+        case N_COLUMN: return column(nd.col);   // (index and type: checked by column_uses before the first launch)
         case N_NUM: r.scalar = true; r.f = nd.num; return r;
         case N_BOOL: r.scalar = true; r.i = nd.bval ? 1 : 0; return r;
         case N_STR: r.is_str_lit = true; r.lit = nd.str; r.scalar = true; return r;
@@ -356,8 +321,8 @@ struct Exec {
                           : nd.fn == QE_FN_CMP_GT ? pn::C_GT : nd.fn == QE_FN_CMP_EQ ? pn::C_EQ : pn::C_NE;
             const int ot = e.nodes[nd.ops[0]].type;
             if (ot == QE_DOUBLE) {
-                // (double)int_column OP integral literal, |L| < 2^53 (strict; see Gen::emit): the conversion is monotone and L is exact, so the
-                // comparison can be done on the integers -- no cast kernel, no 8-byte temporary (same rule as Gen::emit)
+                // (double)int_column OP integral literal that exact_integer_literal accepts: compared on the integers -- no cast
+                // kernel, no 8-byte temporary.  The compare kernel runs at the column's width: the literal must fit an INT32 column.
                 auto int_child = [&](int id) {
                     const Node &x = e.nodes[id];
                     if (x.kind != N_CAST || x.type != QE_DOUBLE) return -1;
@@ -366,9 +331,7 @@ struct Exec {
                 };
                 auto int_lit = [&](int id, int ctype, long long &v) {
                     const Node &x = e.nodes[id];
-                    if (x.kind != N_NUM || x.num != std::floor(x.num) || std::fabs(x.num) >= 9007199254740992.0) return false;
-                    v = (long long)x.num;
-                    return ctype == QE_INT64 || (v >= -2147483648ll && v <= 2147483647ll);
+                    return x.kind == N_NUM && exact_integer_literal(x.num, v) && (ctype == QE_INT64 || (v >= -2147483648ll && v <= 2147483647ll));
                 };
                 const int ia = int_child(nd.ops[0]), ib = int_child(nd.ops[1]);
                 long long lit = 0;
@@ -391,28 +354,16 @@ struct Exec {
             Vec a = numeric ? operand(e, nd.ops[0]) : eval(e, nd.ops[0]), b = numeric ? operand(e, nd.ops[1]) : eval(e, nd.ops[1]);
             r.valid = and_valid(a.valid, b.valid);
             if (ot == QE_STRING) {
-                const bool eqne = cmp == pn::C_EQ || cmp == pn::C_NE;
-                if (a.is_str_lit && b.is_str_lit) {
-                    const int c = utf16_compare(a.lit, b.lit);
+                const StringCompare sc = plan_string_compare(nd.fn, side(a), side(b));
+                if (sc.kind == StringCompare::Constant) {
                     r.scalar = true;
-                    r.i = (cmp == pn::C_LT ? c < 0 : cmp == pn::C_LE ? c <= 0 : cmp == pn::C_GE ? c >= 0 : cmp == pn::C_GT ? c > 0
-                           : cmp == pn::C_EQ ? c == 0 : c != 0) ? 1 : 0;
+                    r.i = sc.value ? 1 : 0;
                     return r;
                 }
-                if (eqne && (a.is_str_lit || b.is_str_lit)) {
-                    // String.equals against a literal == code equality (absent literal: code -1, never equal)
-                    if (a.is_str_lit) { a.i = b.dict->find(a.lit); a.is_str_lit = false; }
-                    else { b.i = a.dict->find(b.lit); b.is_str_lit = false; }
-                } else if (!(eqne && a.dict == b.dict)) {
-                    // String.compareTo / equals across dictionaries: dense ranks in one merged compareTo order, compared as INT32
-                    const std::vector<std::string> lit_a{a.lit}, lit_b{b.lit};
-                    const std::vector<std::string> *la = a.is_str_lit ? &lit_a : &a.dict->entries;
-                    const std::vector<std::string> *lb = b.is_str_lit ? &lit_b : &b.dict->entries;
-                    std::vector<std::vector<int32_t>> ranks = merged_ranks({la, lb});
-                    if (a.is_str_lit) { a.i = ranks[0][0]; a.is_str_lit = false; }
-                    else { a.data = lookup(ranks[0], a); }
-                    if (b.is_str_lit) { b.i = ranks[1][0]; b.is_str_lit = false; }
-                    else { b.data = lookup(ranks[1], b); }
+                Vec *x[2] = {&a, &b};
+                for (int i = 0; i < 2; i++) {   // a literal side: its code / rank; a dictionary side: its codes, or their ranks as an INT32 column
+                    if (x[i]->is_str_lit) { x[i]->i = sc.lit[i]; x[i]->is_str_lit = false; }
+                    else if (sc.kind == StringCompare::Ranks) x[i]->data = lookup(sc.table[i], *x[i]);
                 }
                 r.data = alloc_words();
                 pn::compare(s, QE_INT32, cmp, 0, opnd(a), opnd(b), (uint64_t *)r.data.get(), n);
@@ -451,9 +402,7 @@ struct Exec {
             Vec c = materialize(eval(e, nd.ops[0])), t = eval(e, nd.ops[1]), f = eval(e, nd.ops[2]);
             Buf cond = c.data;
             if (c.valid) cond = and_valid(c.data, c.valid);   // c = vc & kc
-            if (nd.type == QE_STRING) {
-                r.dict = unify_dictionaries(t, f);
-            }
+            if (nd.type == QE_STRING) r.dict = unify(t, f);
             if (nd.type == QE_BOOLEAN) {
                 Vec tt = materialize(t), ff = materialize(f);
                 r.data = alloc_words();
@@ -486,7 +435,7 @@ struct Exec {
         case QE_FN_COALESCE: {   // select on the first operand's validity words; NULL iff both operands are
             Vec a = eval(e, nd.ops[0]), b = eval(e, nd.ops[1]);
             if (!a.valid) return a;   // never NULL: the node is its first operand
-            if (nd.type == QE_STRING) r.dict = unify_dictionaries(a, b);
+            if (nd.type == QE_STRING) r.dict = unify(a, b);
             if (nd.type == QE_BOOLEAN) {
                 Vec bb = materialize(b);
                 r.data = alloc_words();
@@ -516,17 +465,6 @@ struct Exec {
     }
 };
 
-void collect_columns(const Expr &e, std::vector<char> &used) {
-    // (the direct operand of a null test is asked for its validity words only: Exec::validity)
-    std::vector<char> null_tested(e.nodes.size(), 0);
-    for (const Node &nd : e.nodes)
-        if (nd.kind == N_FN && (nd.fn == QE_FN_IS_NULL || nd.fn == QE_FN_IS_NOT_NULL)) null_tested[(size_t)nd.ops[0]] = 1;
-    for (size_t id = 0; id < e.nodes.size(); id++) {
-        const Node &nd = e.nodes[id];
-        if (nd.kind == N_COLUMN && !null_tested[id] && nd.col >= 0 && nd.col < (int)used.size()) used[nd.col] = 1;
-    }
-}
-
 }  // namespace
 
 qe_result *run_per_node(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filter, const qe_expr *const *projs,
@@ -555,24 +493,25 @@ qe_result *run_per_node(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filte
     // A value column that the whole plan uses exactly once, as a direct operand of an arithmetic or comparison node, is never
     // gathered into a narrowed domain: the node reads it through the row ids (cfg 2: `a + b` after the filter -- 0.8 GB less
     // written and 0.8 GB less read per 1 B rows; cfg 3: `l_quantity < 24`, `l_extendedprice * ..`).
+    std::vector<char> proj_values(x.env.size(), 0);   // columns whose VALUES the projections read (a null test asks for the validity only)
     {
-        std::vector<int> refs(x.env.size(), 0), direct(x.env.size(), 0);
-        auto scan = [&](const Expr &pe) {
-            for (const Node &nd : pe.nodes) {
-                if (nd.kind == N_COLUMN && nd.col >= 0 && nd.col < (int)refs.size()) refs[(size_t)nd.col]++;
-                const bool arith = nd.kind == N_FN && (nd.fn == QE_FN_ADD || nd.fn == QE_FN_SUB || nd.fn == QE_FN_MUL || nd.fn == QE_FN_DIV || nd.fn == QE_FN_MOD);
-                const bool cmp = nd.kind == N_FN && (nd.fn == QE_FN_CMP_LT || nd.fn == QE_FN_CMP_LE || nd.fn == QE_FN_CMP_GE || nd.fn == QE_FN_CMP_GT ||
-                                                     nd.fn == QE_FN_CMP_EQ || nd.fn == QE_FN_CMP_NE);
-                if (arith || cmp)
-                    for (int op : nd.ops) {
-                        const Node &on = pe.nodes[(size_t)op];
-                        if (on.kind == N_COLUMN && on.col >= 0 && on.col < (int)refs.size()) direct[(size_t)on.col]++;
-                    }
+        std::vector<int> col_types, refs(x.env.size(), 0), direct(x.env.size(), 0);
+        for (const Column &c : batch->cols) col_types.push_back(c.type);
+        auto scan = [&](const Expr &pe, bool projection) {
+            for (const ColumnUse &u : column_uses(pe, pe.root, col_types)) {   // (raises the plan's column errors before the first launch)
+                refs[(size_t)u.col]++;
+                if (projection && u.value) proj_values[(size_t)u.col] = 1;
             }
+            for (const Node &nd : pe.nodes)
+                if (nd.kind == N_FN && (is_arithmetic_fn(nd.fn) || is_comparison_fn(nd.fn)))
+                    for (int op : nd.ops)
+                        if (pe.nodes[(size_t)op].kind == N_COLUMN) direct[(size_t)pe.nodes[(size_t)op].col]++;
         };
-        if (filter) scan(filter->e);
-        for (int32_t i = 0; i < nproj; i++)
-            if (projs[i]) scan(projs[i]->e);
+        if (filter) scan(filter->e, false);
+        for (int32_t i = 0; i < nproj; i++) {
+            if (!projs[i]) fail(QE_ERR_INVALID_ARG, "null projection");
+            scan(projs[i]->e, true);
+        }
         x.through_ids.assign(x.env.size(), 0);
         for (size_t j = 0; j < x.env.size(); j++)
             x.through_ids[j] = refs[j] == 1 && direct[j] == 1 && !x.base[j].valid &&
@@ -582,14 +521,7 @@ qe_result *run_per_node(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filte
     if (filter && batch->nrows > 0) {
         const Expr &fe = filter->e;
         if (fe.nodes[fe.root].type != QE_BOOLEAN) fail(QE_ERR_PROGRAM, "filter expression must be BOOLEAN");
-        // 1. the conjuncts of the top-level AND chain, left to right
-        std::vector<int> conj;
-        std::function<void(int)> split = [&](int id) {
-            const Node &nd = fe.nodes[id];
-            if (nd.kind == N_FN && nd.fn == QE_FN_AND && nd.ops.size() == 2) { split(nd.ops[0]); split(nd.ops[1]); }
-            else conj.push_back(id);
-        };
-        split(fe.root);
+        const std::vector<int> conj = split_conjuncts(fe, fe.root);   // 1. the top-level AND chain, left to right
         unsigned long long *d_total = (unsigned long long *)(ctx->d_ctrl + 2);
         Buf acc;   // keep mask accumulated over the conjuncts evaluated in the current domain since it was last narrowed
         for (size_t ci = 0; ci < conj.size() && x.n > 0; ci++) {
@@ -617,22 +549,16 @@ qe_result *run_per_node(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filte
         }
         m = x.n;
         // 3. the projections' columns that the final domain has not seen yet: one gather launch
-        std::vector<char> used(x.env.size(), 0);
-        for (int32_t i = 0; i < nproj; i++) collect_columns(projs[i]->e, used);
-        x.prefetch(used);
+        x.prefetch(proj_values);
     }
     // 4. projections over the (compacted) domain
     res->count = m;
     res->capacity = m;
     for (int32_t i = 0; i < nproj; i++) {
-        if (!projs[i]) fail(QE_ERR_INVALID_ARG, "null projection");
         const Expr &pe = projs[i]->e;
         Vec v = x.eval(pe, pe.root);
         if (v.is_str_lit) {   // SELECT 'lit'
-            auto ndct = std::make_shared<DictData>();
-            ndct->entries.push_back(v.lit);
-            ndct->index[v.lit] = 0;
-            v.dict = ndct;
+            v.dict = literal_dictionary(v.lit);
             v.i = 0;
             v.is_str_lit = false;
         }

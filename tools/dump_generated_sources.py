@@ -134,6 +134,21 @@ def run_option_set(repo, out, name, tuning, cmp, scope):
             fe(Fn.CMP_LE, a, num(2.5)), fe(Fn.CMP_LT, num(2.5), a), fe(Fn.CMP_LE, num(2.5), a), fe(Fn.CMP_GE, num(2.5), a), fe(Fn.CMP_LT, p, p),
             fe(Fn.CMP_LT, b, c), fe(Fn.CMP_EQ, b, num(3)), fe(Fn.OR, p, fe(Fn.CMP_LT, a, num(1))), fe(Fn.AND, p, fe(Fn.NOT, p))])
         fp(cols, fe(Fn.CMP_LT, a, num(1)), [fe(Fn.ADD, a, num(i)) for i in range(16)])      # wide enough to halve threads / unroll
+        # null tests over a column and over an expression, as filter conjuncts and as projections; columns that only null tests read
+        lit = StringLiteralExpression
+        fp(cols, fe(Fn.AND, fe(Fn.IS_NOT_NULL, a), fe(Fn.IS_NULL, fe(Fn.ADD, b, c))),
+           [fe(Fn.IS_NULL, a), fe(Fn.IS_NOT_NULL, s), fe(Fn.IS_NULL, fe(Fn.ADD, a, b)), fe(Fn.IS_NOT_NULL, fe(Fn.CMP_LT, s, s2)), fe(Fn.IS_NULL, num(1)), b])
+        fp(cols, fe(Fn.IS_NULL, p), [fe(Fn.IS_NOT_NULL, c), fe(Fn.IS_NULL, s2)])
+        # COALESCE over numeric, BOOLEAN and STRING operands: one dictionary, two, column against literal (present / absent), literal first
+        fp(cols, fe(Fn.COALESCE, p, fe(Fn.CMP_LT, a, num(1))),
+           [fe(Fn.COALESCE, a, b), fe(Fn.COALESCE, c, num(0)), fe(Fn.COALESCE, b, c), fe(Fn.COALESCE, p, BooleanLiteralExpression(False)),
+            fe(Fn.COALESCE, s, s), fe(Fn.COALESCE, s, s2), fe(Fn.COALESCE, s, lit("none")), fe(Fn.COALESCE, s, lit("fig")),
+            fe(Fn.COALESCE, lit("x"), s2), fe(Fn.COALESCE, lit("x"), lit("y")), fe(Fn.COALESCE, fe(Fn.IF, p, s, s2), lit("kiwi"))])
+        fp(cols, fe(Fn.CMP_LT, fe(Fn.ABS, a), num(1)), [fe(f, x) for f in (Fn.ABS, Fn.FLOOR, Fn.CEIL) for x in (a, b, c)])
+        # the integer shortcut of (double)int OP literal through identity nodes (unary plus, FLOOR of an integer), and what must not take it
+        fp(cols, fe(Fn.CMP_LT, fe(Fn.UNARY_PLUS, b), num(7)),
+           [fe(Fn.CMP_GE, num(3), fe(Fn.UNARY_PLUS, c)), fe(Fn.CMP_EQ, fe(Fn.FLOOR, b), num(2)), fe(Fn.CMP_LT, fe(Fn.ABS, c), num(2.0 ** 53)),
+            fe(Fn.CMP_LE, b, num(2.0 ** 53 - 1)), fe(Fn.CMP_GT, b, num(-2.0 ** 53)), fe(Fn.CMP_LT, c, num(0.5))])
     if "small" in scope:
         cols = [dcol(True), icol(), i32col(), bcol(True), scol(d1), scol(d2)]
         fp(cols, fe(Fn.AND, p, fe(Fn.CMP_LT, a, num(1))), [a, p, s])
