@@ -58,6 +58,10 @@ enum {
  *   QE_OP_NUM_LITERAL  u8 op, f64 value                   NumericLiteralExpression :17-21 (always DOUBLE)
  *   QE_OP_BOOL_LITERAL u8 op, u8 value                    BooleanLiteralExpression :23-27
  *   QE_OP_STR_LITERAL  u8 op, u16 nbytes, UTF-8 bytes     StringLiteralExpression :29-33
+ *   QE_OP_LIST_LITERAL u8 op, u8 elem_type, u32 count,    extension: the literal list of IN.  elem_type is QE_DOUBLE,
+ *                      count payloads                     QE_STRING or QE_BOOLEAN; a payload is an f64, or u16 nbytes +
+ *                                                         UTF-8 bytes, or a u8.  Pushes ONE value (the whole list);
+ *                                                         1 <= count <= 65536; only IN may consume it
  *   QE_OP_FUNCTION     u8 op, u8 function, u8 type        FunctionExpression :36-45; function = Function.ordinal
  *                                                         (ast/Functions.kt:7-22), type = dataTypeNullable or 0xFF
  *
@@ -65,20 +69,30 @@ enum {
  * plus the bytecode verifier pass (BytecodeCompiler.kt:138, MaxStackVisitor :177-196):
  * it checks stack discipline, arity and operand types and infers result types.
  */
-enum { QE_OP_COLUMN = 1, QE_OP_NUM_LITERAL = 2, QE_OP_BOOL_LITERAL = 3, QE_OP_STR_LITERAL = 4, QE_OP_FUNCTION = 16 };
+enum { QE_OP_COLUMN = 1, QE_OP_NUM_LITERAL = 2, QE_OP_BOOL_LITERAL = 3, QE_OP_STR_LITERAL = 4, QE_OP_LIST_LITERAL = 5, QE_OP_FUNCTION = 16 };
 
-/* Ordinals 0-16 are the reference's (ast/Functions.kt:7-22).  Ordinals 17-22 are extensions the reference's
+/* Ordinals 0-16 are the reference's (ast/Functions.kt:7-22).  Ordinals 17-22, 24 and 25 are extensions the reference's
  * enum does not have (additive: header version and ABI version stay 1):
  *   IS_NULL / IS_NOT_NULL  1 operand of any type -> BOOLEAN, never NULL: the validity of the operand EXPRESSION
  *   COALESCE               2 operands typed like the branches of IF -> a where a is valid, else b (NULL iff both are)
  *   ABS                    numeric -> operand type; Math.abs (-0.0 -> 0.0, NaN stays NaN, MIN_VALUE stays MIN_VALUE)
  *   FLOOR / CEIL           numeric -> operand type; Math.floor / Math.ceil on DOUBLE, the identity on integers
+ *   IN                     (value, list literal) -> BOOLEAN, NULL exactly where the value is.  By definition
+ *                          value = L1 OR .. OR value = Lm under CMP_EQ on the promoted operands: the value and the list are
+ *                          typed as the operands of CMP_EQ (an integer value is cast to DOUBLE, every numeric literal being
+ *                          DOUBLE); DOUBLE compares as Double.equals (one NaN, -0.0 <> 0.0) in both cmp_semantics.  Duplicates
+ *                          are allowed, an empty list is a program error, more than 65536 items are QE_ERR_UNSUPPORTED
+ *                          (a larger set is a SEMI join).  NOT IN is NOT(IN(..)).
+ *   LIKE                   (STRING value, STRING literal pattern) -> BOOLEAN, NULL exactly where the value is.  Whole-string,
+ *                          case-sensitive match by code points (an invalid UTF-8 byte is its own unit): % matches zero or more,
+ *                          _ exactly one, \ makes the next character literal (a trailing lone \ is a program error).
  * ABS, FLOOR and CEIL map NULL to NULL. */
 enum {
     QE_FN_AND = 0, QE_FN_OR, QE_FN_IF, QE_FN_NOT, QE_FN_UNARY_MINUS, QE_FN_UNARY_PLUS, QE_FN_MUL, QE_FN_DIV,
     QE_FN_MOD, QE_FN_ADD, QE_FN_SUB, QE_FN_CMP_LT, QE_FN_CMP_LE, QE_FN_CMP_GE, QE_FN_CMP_GT, QE_FN_CMP_EQ,
     QE_FN_CMP_NE,
-    QE_FN_IS_NULL = 17, QE_FN_IS_NOT_NULL, QE_FN_COALESCE, QE_FN_ABS, QE_FN_FLOOR, QE_FN_CEIL, QE_FN_COUNT_
+    QE_FN_IS_NULL = 17, QE_FN_IS_NOT_NULL, QE_FN_COALESCE, QE_FN_ABS, QE_FN_FLOOR, QE_FN_CEIL, /* 23 is not assigned: unknown */
+    QE_FN_IN = 24, QE_FN_LIKE = 25, QE_FN_COUNT_
 };
 
 /* ast/Functions.kt:24-26 ordinals (ANY/ALL are TODO() in the reference: Accumulators.kt:16-17) */

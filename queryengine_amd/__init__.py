@@ -2,7 +2,7 @@
 of jhorstmann/queryengine."""
 from .datatypes import DataType, Field, Schema, promote  # noqa: F401
 from .ast import (  # noqa: F401
-    Function, FunctionType, AggregationFunction, Expression, IdentifierExpression, NumericLiteralExpression,
+    Function, SetFunction, FunctionType, AggregationFunction, Expression, IdentifierExpression, NumericLiteralExpression,
     BooleanLiteralExpression, StringLiteralExpression, FunctionExpression, AggregationFunctionExpression,
     ColumnExpression, ExpressionVisitor, DefaultExpressionVisitor,
 )

@@ -3,7 +3,7 @@
 Mirrors ``ast/Expressions.kt:6-62`` (node classes), ``ast/Functions.kt:3-26``
 (``FunctionType``, ``Function`` with type and arity; ordinals 0-16 identical to the
 Kotlin enum so that the serialised program is what a Kotlin-side serialiser
-would emit from ``Function.ordinal``; 17-22 are extensions the enum does not have) and ``ast/ExpressionVisitor.kt:3-13``.
+would emit from ``Function.ordinal``; 17-22 are extensions the enum does not have; ``SetFunction`` holds the set-membership extensions 24-25) and ``ast/ExpressionVisitor.kt:3-13``.
 """
 from __future__ import annotations
 
@@ -64,6 +64,42 @@ class Function(enum.Enum):
     @property
     def arity(self) -> int:
         return self.value[2]
+
+    @property
+    def variable_arity(self) -> bool:
+        """``arity`` is a lower bound: the function takes at least that many operands."""
+        return False
+
+
+class SetFunction(enum.Enum):
+    """Set-membership functions: the second operand is a set fixed at plan time, not a value (QE_FN_IN / QE_FN_LIKE of
+    include/qe_hip.h).  They are a ``FunctionExpression``'s ``function`` like a ``Function`` and have the same properties;
+    they are kept apart from ``Function`` because that enum mirrors value functions, whose operands are all expressions.
+    Wire ordinal 23 is not assigned."""
+    # IN's operands are [value, literal, literal, ...]: `arity` is the LEAST number of operands (variable_arity)
+    IN = (24, FunctionType.COMPARISON, 2)
+    LIKE = (25, FunctionType.COMPARISON, 2)      # [value, pattern literal]
+
+    @property
+    def is_extension(self) -> bool:
+        return True
+
+    @property
+    def ordinal(self) -> int:
+        return self.value[0]
+
+    @property
+    def type(self) -> FunctionType:
+        return self.value[1]
+
+    @property
+    def arity(self) -> int:
+        return self.value[2]
+
+    @property
+    def variable_arity(self) -> bool:
+        """``arity`` is a lower bound: the function takes at least that many operands."""
+        return self is SetFunction.IN
 
 
 class AggregationFunction(enum.IntEnum):
@@ -147,7 +183,7 @@ class StringLiteralExpression(Expression):
 
 @dataclass(frozen=True)
 class FunctionExpression(Expression):
-    function: Function
+    function: "Function | SetFunction"
     operands: Sequence[Expression]
     dataTypeNullable: Optional[DataType] = None
 

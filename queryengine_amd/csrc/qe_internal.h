@@ -25,7 +25,7 @@ void hip_check(hipError_t e, const char *what, const char *file, int line);
 #define QE_HIP(x) ::qe::hip_check((x), #x, __FILE__, __LINE__)
 
 // ---- IR: typed expression tree ------------------------------------------------------
-enum NodeKind { N_COLUMN = 0, N_NUM = 1, N_BOOL = 2, N_STR = 3, N_FN = 4, N_CAST = 5 };
+enum NodeKind { N_COLUMN = 0, N_NUM = 1, N_BOOL = 2, N_STR = 3, N_FN = 4, N_CAST = 5, N_LIST = 6 };
 
 struct Node {
     int kind = 0;
@@ -35,6 +35,10 @@ struct Node {
     double num = 0.0;   // N_NUM
     bool bval = false;  // N_BOOL
     std::string str;    // N_STR
+    // N_LIST (the literal list of IN; `type` = its element type): the values of the one kind it holds
+    std::vector<double> list_num;
+    std::vector<std::string> list_str;
+    std::vector<char> list_bool;
     std::vector<int> ops;
 };
 
@@ -76,6 +80,8 @@ struct DictData {
 // java.lang.String.compareTo (BytecodeCompiler.kt:303, Interpreter.kt:104-107) on UTF-8 input: lexicographic order of
 // the UTF-16 code units (a supplementary character sorts as its surrogate pair, i.e. BEFORE U+E000..U+FFFF).
 int utf16_compare(const std::string &a, const std::string &b);
+// The code points of UTF-8 input as that comparison decodes them: an invalid byte is its own unit.
+std::vector<uint32_t> utf8_code_points(const std::string &s);
 // Dense ranks of the strings of several lists in ONE merged compareTo order: rank[l][i] of lists[l][i]; equal strings get
 // equal ranks, so every comparison of two strings is the same comparison of their ranks.
 std::vector<std::vector<int32_t>> merged_ranks(const std::vector<const std::vector<std::string> *> &lists);

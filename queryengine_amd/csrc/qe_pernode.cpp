@@ -222,6 +222,79 @@ struct Exec {
     }
     std::vector<Buf> keep_dev;
 
+    // a plan constant table (membership bits / hash set) on the device
+    Buf upload(const std::vector<int32_t> &table) {
+        auto host = std::make_shared<std::vector<int32_t>>(table);
+        keep_tables.push_back(host);
+        Buf dev = alloc(std::max<size_t>(host->size() * 4, 16));
+        if (!host->empty()) QE_HIP(hipMemcpyAsync(dev.get(), host->data(), host->size() * 4, hipMemcpyHostToDevice, s));
+        keep_dev.push_back(dev);
+        return dev;
+    }
+
+    // IN / LIKE: carries plan_member out.  Every route that is no constant goes through a table (a compare chain is an economy of
+    // the fused kernel's text only): pn::member_bits or pn::member_hash.  The result shares the value's validity words.
+    Vec member(const Expr &e, int id) {
+        const Node &nd = e.nodes[id];
+        const Node &vn = e.nodes[nd.ops[0]];
+        Vec r;
+        r.type = QE_BOOLEAN;
+        int int_node = -1;
+        if (vn.kind == N_CAST && vn.type == QE_DOUBLE) {
+            const Node &c = e.nodes[vn.ops[0]];
+            if ((c.type == QE_INT64 || c.type == QE_INT32) && c.kind != N_NUM) int_node = vn.ops[0];
+        }
+        MemberPlan mp;
+        Vec a;
+        if (vn.type == QE_STRING && vn.kind == N_COLUMN) {   // a folded test asks the column for its validity only
+            mp = plan_member(e, id, StrSide{base[(size_t)vn.col].dict.get(), nullptr}, -1);
+            if (mp.kind == MemberPlan::Constant) {
+                r.scalar = true;
+                r.i = mp.value ? 1 : 0;
+                r.valid = validity(e, nd.ops[0]);
+                return r;
+            }
+            a = eval(e, nd.ops[0]);
+        } else if (vn.type == QE_STRING) {
+            a = eval(e, nd.ops[0]);
+            mp = plan_member(e, id, side(a), -1);
+        } else {
+            mp = plan_member(e, id, StrSide{nullptr, nullptr}, int_node >= 0 ? e.nodes[int_node].type : -1);
+            a = eval(e, mp.on_int ? int_node : nd.ops[0]);
+        }
+        r.valid = a.valid;
+        switch (mp.kind) {
+        case MemberPlan::Constant:
+            r.scalar = true;
+            r.i = mp.value ? 1 : 0;
+            return r;
+        case MemberPlan::Copy: a.valid = r.valid; return a;
+        case MemberPlan::Negate:
+            a = materialize(a);
+            r.data = alloc_words();
+            pn::word_not(s, (const uint64_t *)a.data.get(), (uint64_t *)r.data.get(), bitmap_words(n));
+            return r;
+        default: break;
+        }
+        a = materialize(a);
+        const int kt = kernel_type(a.type);
+        r.data = alloc_words();
+        if (mp.kind == MemberPlan::Bits) {
+            pn::member_bits(s, kt, a.data.get(), mp.base, mp.nbits, (const uint32_t *)upload(mp.table).get(), (uint64_t *)r.data.get(), n);
+            return r;
+        }
+        if (mp.kind == MemberPlan::Chain) {   // the same members as a hash set
+            const MemberHashSet hs = build_member_hash(std::vector<uint64_t>(mp.chain.begin(), mp.chain.end()));
+            mp.table.clear();
+            for (uint64_t w : hs.words) {
+                mp.table.push_back((int32_t)(uint32_t)w);
+                mp.table.push_back((int32_t)(uint32_t)(w >> 32));
+            }
+        }
+        pn::member_hash(s, kt, a.data.get(), (const uint64_t *)upload(mp.table).get(), (uint64_t *)r.data.get(), n);
+        return r;
+    }
+
     Buf ones() {
         Buf r = alloc_words();
         pn::word_fill(s, ~0ull, (uint64_t *)r.get(), bitmap_words(n));
@@ -460,6 +533,7 @@ struct Exec {
             pn::unary(s, nd.type, nd.fn == QE_FN_ABS ? pn::U_ABS : nd.fn == QE_FN_FLOOR ? pn::U_FLOOR : pn::U_CEIL, a.data.get(), r.data.get(), n);
             return r;
         }
+        case QE_FN_IN: case QE_FN_LIKE: return member(e, id);
         default: fail(QE_ERR_INTERNAL, "bad function");
         }
     }
@@ -498,7 +572,10 @@ qe_result *run_per_node(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filte
         std::vector<int> col_types, refs(x.env.size(), 0), direct(x.env.size(), 0);
         for (const Column &c : batch->cols) col_types.push_back(c.type);
         auto scan = [&](const Expr &pe, bool projection) {
-            for (const ColumnUse &u : column_uses(pe, pe.root, col_types)) {   // (raises the plan's column errors before the first launch)
+            std::vector<std::shared_ptr<DictData>> dicts;
+            for (const Column &c : batch->cols) dicts.push_back(c.dict);
+            const std::vector<char> folded = constant_column_members(pe, dicts);   // an IN / LIKE folded to a constant reads the validity only
+            for (const ColumnUse &u : column_uses(pe, pe.root, col_types, &folded)) {   // (raises the plan's column errors before the first launch)
                 refs[(size_t)u.col]++;
                 if (projection && u.value) proj_values[(size_t)u.col] = 1;
             }

@@ -54,5 +54,12 @@ void gather_multi(hipStream_t s, const GatherArgs &a);
 // out[i] = table[codes[i]] (a code outside the table -- the garbage under a NULL -- reads as -1): string ranks / code remaps
 void lookup_codes(hipStream_t s, const int32_t *table, int32_t ntable, const int32_t *codes, int32_t *out, int64_t n);
 
+// Set membership (IN / LIKE) -> value bitmap, written the way compare writes it; bits of rows >= n are 0.
+// member_bits: bit (value - base) of the 32-bit words `table`, false outside [0, nbits); type QE_INT32 (dictionary codes too) / QE_INT64.
+void member_bits(hipStream_t s, int type, const void *values, long long base, long long nbits, const uint32_t *table, uint64_t *out, int64_t n);
+// member_hash: probe of the open-addressing set `table` ({mask | probe << 32, home mask, EMPTY, 0, slots..}, qe_expr_rules.h) with
+// the 64-bit image of the value: an INT32 / INT64 value itself, the canonical bits (Double.doubleToLongBits) of a DOUBLE.
+void member_hash(hipStream_t s, int type, const void *values, const uint64_t *table, uint64_t *out, int64_t n);
+
 }  // namespace pn
 }  // namespace qe

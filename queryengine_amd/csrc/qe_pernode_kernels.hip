@@ -578,5 +578,57 @@ void lookup_codes(hipStream_t s, const int32_t *table, int32_t ntable, const int
     hipLaunchKernelGGL(k_lookup_codes, dim3(grid_for(n)), dim3(256), 0, s, (const int *)table, (int)ntable, (const int *)codes, (int *)out, (i64)n);
 }
 
+// ---- set membership (IN / LIKE) ---------------------------------------------------------------------------------------
+// The tables are read with ordinary cached loads: a table is small and every wave reads it, it stays in L2 beside the stream.
+template <typename T> __global__ void __launch_bounds__(256) k_member_bits(const T *v, i64 base, u64 nbits, const u32 *table, u64 *out, i64 n) {
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    const i64 padded = (n + 63) & ~63ll;
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += stride) {
+        bool r = false;
+        if (i < n) {
+            const u64 idx = (u64)(i64)v[i] - (u64)base;   // the garbage under a NULL lands outside [0, nbits) or on a bit nobody keeps
+            if (idx < nbits) r = ((table[idx >> 5] >> (u32)(idx & 31ull)) & 1u) != 0u;
+        }
+        const u64 w = __ballot(r);
+        if ((threadIdx.x & 63) == 0) out[i >> 6] = w;
+    }
+}
+void member_bits(hipStream_t s, int type, const void *values, long long base, long long nbits, const uint32_t *table, uint64_t *out, int64_t n) {
+    if (n <= 0) return;
+    const int g = grid_for(n);
+    if (type == QE_INT64) hipLaunchKernelGGL(k_member_bits<i64>, dim3(g), dim3(256), 0, s, (const i64 *)values, (i64)base, (u64)nbits, (const u32 *)table, (u64 *)out, (i64)n);
+    else hipLaunchKernelGGL(k_member_bits<int>, dim3(g), dim3(256), 0, s, (const int *)values, (i64)base, (u64)nbits, (const u32 *)table, (u64 *)out, (i64)n);
+}
+
+template <typename T> __device__ __forceinline__ u64 member_image(T v) { return (u64)(i64)v; }
+template <> __device__ __forceinline__ u64 member_image<double>(double v) {
+    return v != v ? 0x7ff8000000000000ull : __builtin_bit_cast(u64, v);   // Double.doubleToLongBits
+}
+template <typename T> __global__ void __launch_bounds__(256) k_member_hash(const T *v, const u64 *table, u64 *out, i64 n) {
+    const u64 h0 = table[0], home_mask = table[1], empty = table[2];   // wave-uniform header
+    const u64 mask = h0 & 0xffffffffull;
+    const u32 probe = (u32)(h0 >> 32);
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    const i64 padded = (n + 63) & ~63ll;
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < padded; i += stride) {
+        bool r = false;
+        if (i < n) {
+            const u64 image = member_image<T>(v[i]);
+            const u64 home = (u64)(u32)((image * 0x9E3779B97F4A7C15ull) >> 32) & home_mask;
+            for (u32 j = 0; j < probe; ++j) r |= table[4 + ((home + j) & mask)] == image;   // independent loads: every address is known up front
+            r = r && image != empty;
+        }
+        const u64 w = __ballot(r);
+        if ((threadIdx.x & 63) == 0) out[i >> 6] = w;
+    }
+}
+void member_hash(hipStream_t s, int type, const void *values, const uint64_t *table, uint64_t *out, int64_t n) {
+    if (n <= 0) return;
+    const int g = grid_for(n);
+    if (type == QE_DOUBLE) hipLaunchKernelGGL(k_member_hash<double>, dim3(g), dim3(256), 0, s, (const double *)values, (const u64 *)table, (u64 *)out, (i64)n);
+    else if (type == QE_INT64) hipLaunchKernelGGL(k_member_hash<i64>, dim3(g), dim3(256), 0, s, (const i64 *)values, (const u64 *)table, (u64 *)out, (i64)n);
+    else hipLaunchKernelGGL(k_member_hash<int>, dim3(g), dim3(256), 0, s, (const int *)values, (const u64 *)table, (u64 *)out, (i64)n);
+}
+
 }  // namespace pn
 }  // namespace qe

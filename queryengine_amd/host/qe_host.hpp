@@ -32,10 +32,10 @@ enum class DataType { STRING = 0, DOUBLE = 1, BOOLEAN = 2, INT64 = 3, INT32 = 4 
 
 enum class Function {
     AND = 0, OR, IF, NOT, UNARY_MINUS, UNARY_PLUS, MUL, DIV, MOD, ADD, SUB, CMP_LT, CMP_LE, CMP_GE, CMP_GT, CMP_EQ, CMP_NE,
-    // extensions (not in ast/Functions.kt; QE_FN_* 17-22).  FunctionExpression serialises the ordinal and leaves the result
+    // extensions (not in ast/Functions.kt; QE_FN_* 17-22, 24, 25; 23 is not assigned).  FunctionExpression serialises the ordinal and leaves the result
     // type to the library (0xFF), which infers it: BOOLEAN for the null tests, the IF rule for COALESCE, the operand's type
-    // for ABS / FLOOR / CEIL
-    IS_NULL = 17, IS_NOT_NULL, COALESCE, ABS, FLOOR, CEIL
+    // for ABS / FLOOR / CEIL, BOOLEAN for IN (operands: the value, then the literals of its list) and LIKE (value, pattern literal)
+    IS_NULL = 17, IS_NOT_NULL, COALESCE, ABS, FLOOR, CEIL, IN = 24, LIKE = 25
 };
 
 enum class Mode { GPU_FUSED, GPU_PER_NODE };
@@ -51,6 +51,10 @@ struct TypeCheckException : std::runtime_error { using std::runtime_error::runti
 struct Expression {
     virtual ~Expression() = default;
     virtual void serialize(std::vector<uint8_t> &out) const = 0;
+    // a literal as an item of IN's list: its element type (QE_DOUBLE / QE_STRING / QE_BOOLEAN), or -1 for what is no literal;
+    // list_payload writes the item without an opcode of its own
+    virtual int list_type() const { return -1; }
+    virtual void list_payload(std::vector<uint8_t> &) const {}
 };
 using ExpressionPtr = std::shared_ptr<const Expression>;
 
@@ -66,17 +70,25 @@ struct NumericLiteralExpression : Expression {
     double value;
     explicit NumericLiteralExpression(double v) : value(v) {}
     void serialize(std::vector<uint8_t> &out) const override { out.push_back(QE_OP_NUM_LITERAL); detail::put(out, value); }
+    int list_type() const override { return QE_DOUBLE; }
+    void list_payload(std::vector<uint8_t> &out) const override { detail::put(out, value); }
 };
 struct BooleanLiteralExpression : Expression {
     bool value;
     explicit BooleanLiteralExpression(bool v) : value(v) {}
     void serialize(std::vector<uint8_t> &out) const override { out.push_back(QE_OP_BOOL_LITERAL); out.push_back(value ? 1 : 0); }
+    int list_type() const override { return QE_BOOLEAN; }
+    void list_payload(std::vector<uint8_t> &out) const override { out.push_back(value ? 1 : 0); }
 };
 struct StringLiteralExpression : Expression {
     std::string value;
     explicit StringLiteralExpression(std::string v) : value(std::move(v)) {}
     void serialize(std::vector<uint8_t> &out) const override {
         out.push_back(QE_OP_STR_LITERAL);
+        list_payload(out);
+    }
+    int list_type() const override { return QE_STRING; }
+    void list_payload(std::vector<uint8_t> &out) const override {
         detail::put(out, (uint16_t)value.size());
         out.insert(out.end(), value.begin(), value.end());
     }
@@ -99,7 +111,19 @@ struct FunctionExpression : Expression {
     FunctionExpression(Function f, std::vector<ExpressionPtr> ops, std::optional<DataType> t = std::nullopt)
         : function(f), operands(std::move(ops)), dataTypeNullable(t) {}
     void serialize(std::vector<uint8_t> &out) const override {
-        for (const auto &op : operands) op->serialize(out);   // postfix: operands first
+        if (function == Function::IN) {   // the value, then ONE list literal built from the literal operands
+            if (operands.size() < 2) throw TypeCheckException("[IN] expects at least 2 operands");
+            operands[0]->serialize(out);
+            const int elem = operands[1]->list_type();
+            for (size_t i = 1; i < operands.size(); i++)
+                if (elem < 0 || operands[i]->list_type() != elem) throw TypeCheckException("the list of IN holds literals of one kind");
+            out.push_back(QE_OP_LIST_LITERAL);
+            out.push_back((uint8_t)elem);
+            detail::put(out, (uint32_t)(operands.size() - 1));
+            for (size_t i = 1; i < operands.size(); i++) operands[i]->list_payload(out);
+        } else {
+            for (const auto &op : operands) op->serialize(out);   // postfix: operands first
+        }
         out.push_back(QE_OP_FUNCTION);
         out.push_back((uint8_t)function);
         out.push_back(dataTypeNullable ? (uint8_t)*dataTypeNullable : 0xFF);

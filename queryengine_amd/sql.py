@@ -7,10 +7,12 @@ available here, and the parser is host-side planning outside the hot path
 SQL text in tests and in bench.py.  It keeps the grammar's precedence, which
 follows the order of the alternatives of ``expression`` (Query.g4:27-40):
 
-    unary (- + NOT)  >  * / %  >  + -  >  comparison, IS [NOT] NULL  >  AND  >  OR
+    unary (- + NOT)  >  * / %  >  + -  >  comparison, IS [NOT] NULL, [NOT] IN / LIKE / BETWEEN  >  AND  >  OR
 
 (note that NOT binds tighter than comparison, as in the reference: ``NOT c IS NULL`` is ``(NOT c) IS NULL``;
-the postfix null tests and n-ary ``COALESCE(a, b, c)`` = ``COALESCE(a, COALESCE(b, c))`` are extensions), all binary
+the postfix null tests and n-ary ``COALESCE(a, b, c)`` = ``COALESCE(a, COALESCE(b, c))`` are extensions, and so are the
+postfixes ``x [NOT] IN (literal, ...)``, ``x [NOT] LIKE 'pattern'`` and ``x [NOT] BETWEEN lo AND hi``; BETWEEN is sugar for
+``x >= lo AND x <= hi`` whose bounds are parsed at additive precedence, so its AND is its own), all binary
 operators left-associative, case-insensitive keywords, numeric literals always
 DOUBLE, unary minus/plus folded into numeric literals
 (ExpressionAstBuilder.kt:104-110).
@@ -22,7 +24,7 @@ from dataclasses import dataclass
 from typing import List, Optional
 
 from .ast import (AggregationFunction, AggregationFunctionExpression, BooleanLiteralExpression, Expression, Function,
-                  FunctionExpression, IdentifierExpression, NumericLiteralExpression, StringLiteralExpression)
+                  FunctionExpression, IdentifierExpression, NumericLiteralExpression, SetFunction, StringLiteralExpression)
 
 
 class SyntaxException(RuntimeError):
@@ -131,8 +133,44 @@ class _Parser:
                 if k != "ident" or v.upper() != "NULL":
                     raise SyntaxException(f"expected NULL but found '{v}'")
                 left = FunctionExpression(Function.IS_NOT_NULL if negated else Function.IS_NULL, [left])
+            elif self.member_word(0) or ((k, v) == ("kw", "NOT") and self.member_word(1)):
+                # postfix x [NOT] IN (..) / LIKE '..' / BETWEEN a AND b (extensions; the three words stay plain identifiers
+                # everywhere else)
+                negated = self.accept("kw", "NOT")
+                word = self.take()[1].upper()
+                if word == "IN":
+                    self.expect("op", "(")
+                    items = [self.list_item()]
+                    while self.accept("op", ","):
+                        items.append(self.list_item())
+                    self.expect("op", ")")
+                    left = FunctionExpression(SetFunction.IN, [left] + items)
+                elif word == "LIKE":
+                    k, v = self.take()
+                    if k != "string":
+                        raise SyntaxException(f"expected a string literal after LIKE but found '{v}'")
+                    left = FunctionExpression(SetFunction.LIKE, [left, StringLiteralExpression(v[1:-1].replace("''", "'"))])
+                else:
+                    lo = self.add()
+                    self.expect("kw", "AND")
+                    hi = self.add()
+                    left = FunctionExpression(Function.AND, [FunctionExpression(Function.CMP_GE, [left, lo]),
+                                                             FunctionExpression(Function.CMP_LE, [left, hi])])
+                if negated:
+                    left = FunctionExpression(Function.NOT, [left])
             else:
                 return left
+
+    def member_word(self, ahead: int) -> bool:
+        k, v = self.toks[min(self.i + ahead, len(self.toks) - 1)]
+        return k == "ident" and v.upper() in ("IN", "LIKE", "BETWEEN")
+
+    def list_item(self) -> Expression:
+        """A literal of an IN list; a signed numeric literal folds as everywhere else."""
+        e = self.unary()
+        if not isinstance(e, (NumericLiteralExpression, StringLiteralExpression, BooleanLiteralExpression)):
+            raise SyntaxException("the list of IN holds literals only")
+        return e
 
     def add(self):
         left = self.mul()
@@ -194,6 +232,8 @@ class _Parser:
                     return e
                 if name in Function.__members__:
                     return FunctionExpression(Function[name], ops)
+                if name in SetFunction.__members__:
+                    return FunctionExpression(SetFunction[name], ops)
                 if name in AggregationFunction.__members__:
                     return AggregationFunctionExpression(AggregationFunction[name], ops)
                 raise SyntaxException(f"Unsupported function {name}")   # :62

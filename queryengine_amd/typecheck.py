@@ -6,13 +6,14 @@ Follows ``evaluator/TypeCheck.kt:38-133`` with four deliberate differences (SURV
     that makes every ``p AND q`` fail);
   * unary operators check one operand (TypeCheck.kt:50-52 indexes operands[1]);
   * numeric = {DOUBLE, INT64, INT32} with Java binary numeric promotion (extension types);
-  * the extension functions IS_NULL / IS_NOT_NULL (any type -> BOOLEAN), COALESCE (typed as IF's branches) and
-    ABS / FLOOR / CEIL (numeric -> the operand's type).
+  * the extension functions IS_NULL / IS_NOT_NULL (any type -> BOOLEAN), COALESCE (typed as IF's branches),
+    ABS / FLOOR / CEIL (numeric -> the operand's type), IN (a value and at least one literal, all literals of one kind, the
+    value typed against that kind as CMP_EQ types its operands) and LIKE (a STRING and a STRING literal).
 """
 from __future__ import annotations
 
-from .ast import (AggregationFunction, AggregationFunctionExpression, DefaultExpressionVisitor, Expression, Function,
-                  FunctionExpression)
+from .ast import (AggregationFunction, AggregationFunctionExpression, BooleanLiteralExpression, DefaultExpressionVisitor,
+                  Expression, Function, FunctionExpression, NumericLiteralExpression, SetFunction, StringLiteralExpression)
 from .datatypes import DataType, promote
 
 
@@ -24,11 +25,18 @@ def _invalid(function, operands) -> TypeCheckException:
     return TypeCheckException(f"Invalid operand types for [{function.name}] [{', '.join(o.dataType.name for o in operands)}]")
 
 
+MAX_LIST_ITEMS = 65536   # the cap of a list literal (include/qe_hip.h)
+_LITERALS = (NumericLiteralExpression, StringLiteralExpression, BooleanLiteralExpression)
+
+
 class _TypeCheckVisitor(DefaultExpressionVisitor):
     def visitFunction(self, expr: FunctionExpression) -> Expression:
         ops = self.visitOperands(expr.operands)
         f = expr.function
-        if len(ops) != f.arity:
+        if f.variable_arity:
+            if len(ops) < f.arity:
+                raise TypeCheckException(f"[{f.name}] expects at least {f.arity} operands, got {len(ops)}")
+        elif len(ops) != f.arity:
             raise TypeCheckException(f"[{f.name}] expects {f.arity} operands, got {len(ops)}")
         B = DataType.BOOLEAN
         if f in (Function.UNARY_MINUS, Function.UNARY_PLUS, Function.ABS, Function.FLOOR, Function.CEIL):
@@ -74,6 +82,24 @@ class _TypeCheckVisitor(DefaultExpressionVisitor):
                     raise _invalid(f, ops)
                 t = ops[0].dataType
             return expr.with_(ops, t)
+        if f == SetFunction.IN:
+            # [value, literal, ...]: the list is of one literal kind, the value against it as CMP_EQ types its operands.  The
+            # message names the value's type and the list's element type (every literal's type when they are mixed).
+            items = ops[1:]
+            if len(items) > MAX_LIST_ITEMS:
+                raise TypeCheckException(f"[IN] takes at most {MAX_LIST_ITEMS} list items, got {len(items)}: use a SEMI join for a larger set")
+            if not all(isinstance(o, _LITERALS) for o in items) or len({type(o) for o in items}) != 1:
+                raise _invalid(f, ops)
+            elem = items[0].dataType
+            if promote(ops[0].dataType, elem) is None and ops[0].dataType != elem:
+                raise _invalid(f, [ops[0], items[0]])
+            return expr.with_(ops, B)
+        if f == SetFunction.LIKE:
+            if ops[0].dataType != DataType.STRING or not isinstance(ops[1], StringLiteralExpression):
+                raise _invalid(f, ops)
+            if (len(ops[1].value) - len(ops[1].value.rstrip("\\"))) % 2 == 1:
+                raise TypeCheckException("LIKE pattern ends in a lone \\")
+            return expr.with_(ops, B)
         raise TypeCheckException(f"unknown function {f}")
 
     def visitAggregationFunction(self, expr: AggregationFunctionExpression) -> Expression:

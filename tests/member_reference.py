@@ -1,0 +1,157 @@
+"""Expectation for IN and LIKE, in the manner of expr_lowering.py (whose apply_new_function it imports).
+
+The C oracle knows the reference's 17 functions.  Bottom-up, every IN / LIKE node (and every node of the six earlier
+extensions) has its value operand projected over ALL rows by the oracle, its own column computed by the numpy restatements
+below, that column appended to the input columns and the node replaced by a ColumnExpression on it; the rest stays the
+oracle's business.
+
+IN is `x = L1 OR .. OR x = Lm` under CMP_EQ on the promoted operands (test_member_cpu.py proves the restatement equal to the
+oracle's OR chain): the value converted to DOUBLE as the cast converts it, Double.doubleToLongBits of both sides, np.isin.
+LIKE is the pattern translated to a Python `re` (DOTALL, fullmatch) over the column's strings: Python strings are sequences
+of code points, which is what the matcher works on.
+"""
+from __future__ import annotations
+
+import re
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+from queryengine_amd import (BooleanLiteralExpression, Column, ColumnExpression, DataType, Function, FunctionExpression,
+                             NumericLiteralExpression, SetFunction, StringLiteralExpression)
+
+from expr_lowering import NEW_FUNCTIONS, apply_new_function, nfn
+
+D, I64, I32, B, S = DataType.DOUBLE, DataType.INT64, DataType.INT32, DataType.BOOLEAN, DataType.STRING
+Fn = Function
+SetFn = SetFunction
+MEMBER_FUNCTIONS = (SetFn.IN, SetFn.LIKE)
+CANONICAL_NAN = np.uint64(0x7FF8000000000000)
+
+
+def literal(v):
+    if isinstance(v, bool):
+        return BooleanLiteralExpression(v)
+    if isinstance(v, str):
+        return StringLiteralExpression(v)
+    return NumericLiteralExpression(float(v))
+
+
+def in_(value, items) -> FunctionExpression:
+    """value IN (items): a typed FunctionExpression whose operands are [value, literal, ...]."""
+    return FunctionExpression(SetFn.IN, [value] + [literal(v) for v in items], B)
+
+
+def like(value, pattern: str) -> FunctionExpression:
+    return FunctionExpression(SetFn.LIKE, [value, StringLiteralExpression(pattern)], B)
+
+
+def mfn(f: Function, *ops) -> FunctionExpression:
+    """expr_lowering.nfn that also knows IN and LIKE."""
+    if f in MEMBER_FUNCTIONS:
+        return FunctionExpression(f, list(ops), B)
+    return nfn(f, *ops)
+
+
+# ---- the restatements -------------------------------------------------------------------------------------------------
+def canonical_bits(x) -> np.ndarray:
+    """java.lang.Double.doubleToLongBits: every NaN is 0x7ff8000000000000, -0.0 keeps its sign bit."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    bits = x.view(np.uint64).copy()
+    bits[np.isnan(x)] = CANONICAL_NAN
+    return bits
+
+
+def np_in(value: Column, items: Sequence) -> Column:
+    """BOOLEAN; NULL exactly where the value is (no literal is NULL)."""
+    if value.type == S:
+        wanted = set(items)
+        member = np.array([s in wanted for s in value.dictionary], dtype=bool)
+        codes = value.data.astype(np.int64)
+        ok = (codes >= 0) & (codes < len(member))               # (under a NULL anything may stand)
+        data = np.zeros(len(value), dtype=bool)
+        data[ok] = member[codes[ok]] if len(member) else False
+    elif value.type == B:
+        data = np.isin(value.data, np.array([bool(v) for v in items], dtype=bool))
+    else:
+        as_double = value.data.astype(np.float64)                # int -> double: round to nearest even, Java's (double) too
+        data = np.isin(canonical_bits(as_double), canonical_bits(np.array([float(v) for v in items], dtype=np.float64)))
+    return Column(B, data, value.valid)
+
+
+def like_regex(pattern: str):
+    out, i = [], 0
+    while i < len(pattern):
+        c = pattern[i]
+        if c == "\\":
+            if i + 1 == len(pattern):
+                raise ValueError("LIKE pattern ends in a lone \\")
+            i += 1
+            out.append(re.escape(pattern[i]))
+        elif c == "%":
+            out.append(".*")
+        elif c == "_":
+            out.append(".")
+        else:
+            out.append(re.escape(c))
+        i += 1
+    return re.compile("".join(out), re.DOTALL)
+
+
+def like_matches(pattern: str, s: str) -> bool:
+    return like_regex(pattern).fullmatch(s) is not None
+
+
+def np_like(value: Column, pattern: str) -> Column:
+    rx = like_regex(pattern)
+    seen = {}
+    data = np.zeros(len(value), dtype=bool)
+    for i, s in enumerate(value.to_list()):
+        if s is None:
+            continue
+        if s not in seen:
+            seen[s] = rx.fullmatch(s) is not None
+        data[i] = seen[s]
+    return Column(B, data, value.valid)
+
+
+def literal_values(ops) -> list:
+    return [o.value for o in ops]
+
+
+# ---- lowering ---------------------------------------------------------------------------------------------------------
+def lower(exprs: Sequence, cols: Sequence[Column], oracle, mode) -> Tuple[List, List[Column]]:
+    """(exprs', cols'): no IN / LIKE / extension node is left in exprs'; cols' = cols + one column per such node."""
+    cols = list(cols)
+
+    def project(ops):
+        # a bare column is taken as it is: the oracle need not look at what stands under its NULLs
+        if all(isinstance(o, ColumnExpression) for o in ops):
+            return [cols[o.index] for o in ops]
+        return oracle.filter_project(cols, None, ops, mode)
+
+    def walk(e):
+        if not isinstance(e, FunctionExpression):
+            return e
+        if e.function == SetFn.IN:
+            out = np_in(project([walk(e.operands[0])])[0], literal_values(e.operands[1:]))
+        elif e.function == SetFn.LIKE:
+            out = np_like(project([walk(e.operands[0])])[0], e.operands[1].value)
+        else:
+            ops = [walk(o) for o in e.operands]
+            if e.function not in NEW_FUNCTIONS:
+                if all(a is b for a, b in zip(ops, e.operands)):
+                    return e
+                return FunctionExpression(e.function, ops, e.dataTypeNullable)
+            out = apply_new_function(e.function, project(ops), e.dataType)
+        assert out.type == e.dataType, (e.function, out.type, e.dataType)
+        cols.append(out)
+        return ColumnExpression(f"${len(cols) - 1}", len(cols) - 1, out.type)
+
+    return [None if e is None else walk(e) for e in exprs], cols
+
+
+def expected_filter_project(oracle, cols, flt, projs, mode=None) -> List[Column]:
+    mode = oracle.BYTECODE_COMPILER if mode is None else mode
+    lowered, lcols = lower([flt] + list(projs), cols, oracle, mode)
+    return oracle.filter_project(lcols, lowered[0], lowered[1:], mode)
