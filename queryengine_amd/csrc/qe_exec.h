@@ -1,7 +1,9 @@
 // qe_exec.h -- what the files behind the C ABI share (not part of the ABI, not exported from libqe_hip.so):
 //   qe_context.cpp   errors, pools, contexts, dictionaries, batches, expression handles, stream calibrations
 //   qe_api.cpp       plan cache + geometry (get_plan), the filter+project executor and its entry points
-//   qe_groupby.cpp   the global aggregate and the GROUP BY routes with their entry points
+//   qe_groupby.cpp   the global aggregate and the GROUP BY routes with their entry points: launches and uploads
+//   qe_group_finish.h / .cpp   what the accumulator words of a group mean and how they become result columns (host only, no HIP;
+//                    exported, like qe_expr_rules.h, so that a test program can link it)
 //   qe_result.cpp    results on the device: how every operator builds one (new_result, add_column, gather_columns), and
 //                    their way to the host
 //   qe_sort.cpp      ORDER BY with top-k, and the stable multi-key radix sort (RadixBuffers, SortDriver) that the join build,

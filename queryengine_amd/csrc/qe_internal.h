@@ -301,7 +301,7 @@ struct CodegenOutput {
     bool hashed = false;         // group-by over arbitrary key tuples (a DOUBLE / INT64 / INT32 key, or too many combinations for a
                                  // dense table): open-addressing hash table, entry = hash_words u64 words
     int hash_words = 0;          // {state, null bits, key words.., first row, (count, acc)..}
-    int table_copies = 1;        // global group table: copies merged on the host (one per XCD)
+    int table_copies = 1;        // global group table: copies (one per XCD); always 1, run_groupby_dense refuses anything else
     std::vector<int> cnt_src;    // per aggregate: the aggregate whose count word holds its count (non-nullable inputs all
                                  // see every kept row of the group: they share the first one's counter, one atomic less each)
     // partitioned group-by (domains that do not fit LDS): rows are first scattered into nparts key-range partitions of

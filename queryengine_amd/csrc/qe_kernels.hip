@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "qe_kernels.h"
+#include "qe_group_finish.h"
 
 namespace qe {
 
@@ -386,19 +387,8 @@ __global__ void __launch_bounds__(256) group_finish_kernel(const GroupFinishArgs
     for (int i = 0; i < a.nagg; ++i) {
         const u64 cnt = live ? acc[1 + 2 * a.cnt_src[i]] : 0ull;
         const u64 raw = live ? acc[2 + 2 * i] : 0ull;
-        double v = 0.0;
-        bool ok = true;
-        switch (a.agg_fn[i]) {
-        case QE_AGG_COUNT: v = (double)cnt; break;                                  // Accumulators.kt:26-36
-        case QE_AGG_SUM: v = __builtin_bit_cast(double, raw); ok = cnt != 0ull; break;   // :47-53 empty => null
-        case QE_AGG_AVG: v = __builtin_bit_cast(double, raw); ok = cnt != 0ull; if (ok) v /= (double)cnt; break;
-        default: {                                                                          // MIN / MAX: undo the ordered key
-            const i64 key = (i64)raw;
-            v = __builtin_bit_cast(double, key ^ ((key >> 63) & 0x7fffffffffffffffll));
-            ok = cnt != 0ull;
-        }
-        }
-        if (!ok) v = 0.0;
+        double v;
+        const bool ok = finish_accumulator(a.agg_fn[i], cnt, raw, v);   // qe_group_finish.h: the host finisher's rule
         if (live) a.agg_data[i][j] = v;
         const u64 vb = __ballot(live && ok);
         if (lane == 0 && live) a.agg_valid[i][j >> 6] = vb;

@@ -6,6 +6,8 @@ sees a lost, a doubled and a misrouted row and that no data set holds an undecid
 One schema and one expression list per route: the data sets differ in data, not in plan, so a plan is compiled once.
 Every test asserts through ctx.last_form and the group count that the intended route ran.  Each test prints the largest
 |got - exact| / bound it saw (`pytest -s` shows it)."""
+import re
+
 import numpy as np
 import pytest
 
@@ -17,6 +19,7 @@ pytestmark = pytest.mark.gpu
 DENSE, HASHED, HASH_PARTITIONED = N.FORM_GROUPBY_DENSE, N.FORM_GROUPBY_HASHED, N.FORM_GROUPBY_HASH_PARTITIONED
 GLOBAL_ATOMICS_DENSE, GLOBAL_ATOMICS_HASHED = 256, 131072                    # debug bits of tuning[5]
 FORCE_HP, HP_HEADER_RECORDS, FINISH_ON_DEVICE = 8388608, 33554432, 67108864
+SCATTER_CLOCKS = 64                                                          # a diagnostic BUILD of the partitioned passes
 
 # route -> (tuning[5], the form that must run, executions per plan, fewest groups, most groups); its key kind, key count and
 # rows are agg_reference.ROUTE_SHAPES[route].  ctx.last_form tells the three forms apart, not the routes inside a form: those
@@ -55,9 +58,10 @@ def contexts(native_lib):
     from queryengine_amd import engine as E
     made = {}
 
-    def get(route: str):
+    def get(route: str, word=None):
         if route not in made:
-            word = ROUTES[route][0] if route in ROUTES else 0
+            if word is None:
+                word = ROUTES[route][0] if route in ROUTES else 0
             made[route] = E.Context(device=0, tuning=[0, 0, 0, 0, 0, word, 0, 0] if word else [])
         return made[route]
     yield get
@@ -157,6 +161,65 @@ def test_group_by_with_one_group_holding_most_rows(contexts, route, name):
 def test_group_by_partitioned_sizes_are_within_the_bound(contexts, n, name):
     """The partitioned passes around their tile (4096 rows) and chunk (16 tiles) edges, on fractional values."""
     _run_groupby(contexts, R.SIZES_ROUTE, name, n=n)
+
+
+# One row past a chunk edge of the partitioned passes, on the key-range form and on the forced hash-partitioned form; each test
+# has contexts of its own (a debug word of its own is a build of its own).
+PASSES_ROUTES, PASSES_ROWS = ("dense_partitioned_3000", "hash_partitioned_lines"), 65_537
+
+
+def _passes_case(contexts, route, purpose, extra_word=0):
+    from queryengine_amd import engine as E
+    (kind, ngroups, _), (word, form, _, _, _) = R.ROUTE_SHAPES[route], ROUTES[route]
+    ctx = contexts(f"{route}/{purpose}", word | extra_word)
+    case = R.Case(kind, R.make_data("same_magnitude", PASSES_ROWS, ngroups))
+    batch = E.DeviceBatch.from_columns(ctx, case.cols)
+    keys, exprs = [ctx.compile(k) for k in case.keys], [ctx.compile(e) for e in case.exprs]
+
+    def execute(flt):
+        res = E.filter_groupby(ctx, batch, ctx.compile(flt) if flt is not None else None, keys, exprs, case.aggs)
+        got, _ = _rows(res)
+        res.free()
+        assert ctx.last_form == form, f"route {route}: ran form {ctx.last_form}, not {form}"
+        return got
+    return case, batch, form, execute
+
+
+@pytest.mark.parametrize("route", PASSES_ROUTES)
+def test_group_by_partitioned_passes_when_the_filter_keeps_no_row(contexts, route):
+    """No record to scatter: 0 groups from the intended form, and the next execution on the same context -- every row kept --
+    is still correct (the passes leave their profile bracket closed and the control words usable), twice over."""
+    from queryengine_amd import FunctionExpression, Function, NumericLiteralExpression, DataType, ColumnExpression
+    case, batch, _, execute = _passes_case(contexts, route, "nothing_kept")
+    y = ColumnExpression("y", len(case.keys) + 1, DataType.INT64)
+    nothing = FunctionExpression(Function.CMP_LT, [y, NumericLiteralExpression(-5000.0)], DataType.BOOLEAN)
+    try:
+        for rep in range(2):
+            assert execute(nothing) == [], f"route {route}, execution {rep}: groups from a filter that keeps no row"
+            R.check_rows(case, False, execute(None), f"route {route}, {PASSES_ROWS} rows, after an empty selection, execution {rep}")
+    finally:
+        batch.free()
+
+
+@pytest.mark.parametrize("route", PASSES_ROUTES)
+def test_group_by_scatter_clocks_diagnostic_prints_one_line_per_scatter(contexts, route, capfd):
+    """tuning[5] bit 64: the diagnostic build of the scatter pass.  The rows are those of the exact reference, and stderr holds
+    exactly one `qe_gb_scatter` phases line per execution (each scatters records), labelled on the hash-partitioned form."""
+    case, batch, form, execute = _passes_case(contexts, route, "scatter_clocks", SCATTER_CLOCKS)
+    try:
+        for filtered in (False, True):
+            capfd.readouterr()
+            got = execute(case.flt if filtered else None)
+            err = capfd.readouterr().err
+            R.check_rows(case, filtered, got, f"route {route}, scatter clocks, {PASSES_ROWS} rows, filter {filtered}")
+            lines = [line for line in err.splitlines() if line.startswith("qe_gb_scatter")]
+            assert len(lines) == 1, f"route {route}, filter {filtered}: {len(lines)} phases lines in {err!r}"
+            assert re.search(r" phases, clocks per wave \(grid \d+ x \d+ waves\): issue loads \d+ \| flush \(stores\) \d+ \| LDS sort \d+ \| "
+                             r"wait loads \+ evaluate \d+ \| chunk drain \d+$", lines[0]), lines[0]
+            assert lines[0].startswith("qe_gb_scatter (hash-partitioned) phases") == (form == HASH_PARTITIONED), lines[0]
+            assert lines[0].startswith("qe_gb_scatter phases") == (form == DENSE), lines[0]
+    finally:
+        batch.free()
 
 
 @pytest.mark.parametrize("name", R.DATASETS)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Group-by aggregation throughput: SELECT s, SUM(v), COUNT(v) FROM t [WHERE v < 0.5] over 1 B rows."""
-import os, sys
+import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from queryengine_amd import engine as E, native as N, workloads as W
 from queryengine_amd.ast import ColumnExpression, Function, FunctionExpression, NumericLiteralExpression
@@ -20,12 +20,14 @@ for nkeys in KEYS:
         args = ([ctx.compile(s)], [ctx.compile(v), ctx.compile(v)], [N.AGG_SUM, N.AGG_COUNT])
         r = E.filter_groupby(ctx, b, cf, *args); ng = r.count; r.free()
         ctx.reset_kernel_time()
+        t0 = time.perf_counter()
         for _ in range(5):
             r = E.filter_groupby(ctx, b, cf, *args); r.free()
+        wall = (time.perf_counter() - t0) * 1e3 / 5   # a whole call: the kernels, the host finisher and the result's way back
         _, tot, n = ctx.kernel_time()
         ms = tot / n
-        print(f"GROUP BY s ({nkeys} keys){' WHERE v < 0.5' if f is not None else ''}: groups {ng} kernel {ms:.3f} ms "
-              f"{rows * 12 / ms / 1e6:.0f} GB/s ({rows / ms / 1e6:.1f} G rows/s)", flush=True)
+        print(f"GROUP BY s ({nkeys} keys){' WHERE v < 0.5' if f is not None else ''}: form {ctx.last_form} groups {ng} kernel {ms:.3f} ms "
+              f"wall {wall:.3f} ms {rows * 12 / ms / 1e6:.0f} GB/s ({rows / ms / 1e6:.1f} G rows/s)", flush=True)
     b.free(); ctx.close()
 
 # Tripdata.kt:27-31 shape: SELECT passenger_count, MIN(fare_amount), MAX(fare_amount) -- grouping by a DOUBLE column (hashed form)
@@ -38,10 +40,12 @@ for nkeys in ([10, 100000] if len(sys.argv) <= 4 else [int(x) for x in sys.argv[
     args = ([ctx.compile(k)], [ctx.compile(v), ctx.compile(v)], [N.AGG_MIN, N.AGG_MAX])
     r = E.filter_groupby(ctx, b, None, *args); ng = r.count; r.free()
     ctx.reset_kernel_time()
+    t0 = time.perf_counter()
     for _ in range(5):
         r = E.filter_groupby(ctx, b, None, *args); r.free()
+    wall = (time.perf_counter() - t0) * 1e3 / 5
     _, tot, n = ctx.kernel_time()
     ms = tot / n
-    print(f"GROUP BY DOUBLE k ({nkeys} distinct values), MIN(v), MAX(v): groups {ng} kernel {ms:.3f} ms "
-          f"{rows * 16 / ms / 1e6:.0f} GB/s = {rows * 16 / ms / 1e6 / 8000:.2f} of 8 TB/s ({rows / ms / 1e6:.1f} G rows/s)", flush=True)
+    print(f"GROUP BY DOUBLE k ({nkeys} distinct values), MIN(v), MAX(v): form {ctx.last_form} groups {ng} kernel {ms:.3f} ms "
+          f"wall {wall:.3f} ms {rows * 16 / ms / 1e6:.0f} GB/s = {rows * 16 / ms / 1e6 / 8000:.2f} of 8 TB/s ({rows / ms / 1e6:.1f} G rows/s)", flush=True)
     b.free(); ctx.close()
