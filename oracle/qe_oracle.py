@@ -253,9 +253,17 @@ def filter_project(cols: Sequence[Column], filter_expr: Optional[A.Expression],
         t = p.dataType
         v = valid[:n].astype(np.bool_)
         if t == DataType.STRING:
-            strs = [C.cast(int(ptr), C.c_char_p).value.decode("utf-8") if ok else None
-                    for ptr, ok in zip(data[:n], v)]
-            result.append(Column.from_values(DataType.STRING, strs))
+            # the rows point into a few strings (dictionary entries, literals): each one is decoded once
+            ptrs, first, inverse = np.unique(data[:n][v], return_index=True, return_inverse=True)
+            dictionary, code_of, code = [], {}, np.zeros(len(ptrs), dtype=np.int32)
+            for u in np.argsort(first):           # order of first appearance; two pointers may hold the same string
+                s = C.cast(int(ptrs[u]), C.c_char_p).value.decode("utf-8")
+                code[u] = code_of.setdefault(s, len(dictionary))
+                if code[u] == len(dictionary):
+                    dictionary.append(s)
+            codes = np.zeros(n, dtype=np.int32)
+            codes[v] = code[inverse.reshape(-1)]
+            result.append(Column(DataType.STRING, codes, v, dictionary))
         elif t == DataType.BOOLEAN:
             result.append(Column(t, data[:n].astype(np.bool_), v))
         else:

@@ -101,6 +101,17 @@ bool exact_integer_literal(double lit, long long &out) {
     return true;
 }
 
+bool exact_integer_literal(double lit, int int_type, long long &out) {
+    return exact_integer_literal(lit, out) && (int_type == QE_INT64 || (int_type == QE_INT32 && out >= INT32_MIN && out <= INT32_MAX));
+}
+
+int integer_cast_operand(const Expr &e, int id) {
+    const Node &x = e.nodes[(size_t)id];
+    if (x.kind != N_CAST || x.type != QE_DOUBLE) return -1;
+    const Node &c = e.nodes[(size_t)x.ops[0]];
+    return (c.type == QE_INT64 || c.type == QE_INT32) && c.kind != N_NUM ? x.ops[0] : -1;
+}
+
 // ---- set membership ------------------------------------------------------------------------------------------------------
 namespace {
 struct LikeItem { enum Kind { Lit, One, Any } kind; uint32_t cp; };

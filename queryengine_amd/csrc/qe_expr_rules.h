@@ -54,6 +54,11 @@ std::shared_ptr<DictData> literal_dictionary(const std::string &lit);
 // True (and `out` = L) when the numeric literal L is integral with |L| < 2^53: `(double)x OP L` over an integer x can then
 // be compared on the integers.
 bool exact_integer_literal(double lit, long long &out);
+// The same, and L fits the width of `int_type` (QE_INT64 / QE_INT32): the comparison runs at the integer operand's width.
+bool exact_integer_literal(double lit, int int_type, long long &out);
+// Node `id` as a cast of an integer expression to DOUBLE, `(double)x` with x INT64 / INT32 and no literal: the node id of x,
+// else -1.  A comparison with an exact integer literal and an IN list of them are then carried out on x itself.
+int integer_cast_operand(const Expr &e, int id);
 
 
 // ---- set membership: x IN (list) and s LIKE pattern ----------------------------------------------------------------------

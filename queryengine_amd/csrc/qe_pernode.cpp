@@ -16,6 +16,7 @@
 #include "qe_pernode.h"
 
 #include <cstdlib>
+#include <cstring>
 #include <algorithm>
 
 #include "qe_exec.h"
@@ -45,6 +46,35 @@ struct Vec {
 
 int kernel_type(int t) { return t == QE_STRING ? QE_INT32 : t; }
 
+// what a buffer holds, as the launchers take it
+uint64_t *words(const Buf &b) { return (uint64_t *)b.get(); }   // bitmap words: BOOLEAN values, validity; hash-set words
+uint32_t *u32(const Buf &b) { return (uint32_t *)b.get(); }     // row ids, scan offsets, 32-bit table words
+int32_t *codes(const Buf &b) { return (int32_t *)b.get(); }     // dictionary codes, INT32 tables
+
+// Value columns to be gathered at the same row ids idx[0..m): one pn::gather_multi per `per_launch` (at most 8) of them, which
+// reads the ids once.  A source stays allocated until the batch is gone, that is until its gather has been launched.
+struct Gather {
+    hipStream_t s;
+    int per_launch;
+    pn::GatherArgs ga{};
+    std::vector<Buf> held;
+    Gather(hipStream_t s, const uint32_t *idx, int64_t m, int per_launch = 8) : s(s), per_launch(per_launch) {
+        ga.idx = idx;
+        ga.m = m;
+    }
+    void add(const Buf &src, const Buf &dst, int width) {
+        ga.src[ga.ncols] = src.get();
+        ga.dst[ga.ncols] = dst.get();
+        ga.width[ga.ncols] = width;
+        held.push_back(src);
+        if (++ga.ncols == per_launch) flush();
+    }
+    void flush() {
+        if (ga.ncols > 0) pn::gather_multi(s, ga);
+        ga.ncols = 0;
+    }
+};
+
 struct Exec {
     qe_ctx *ctx;
     hipStream_t s;
@@ -57,31 +87,34 @@ struct Exec {
     std::vector<char> through_ids;
     int ieee;
 
+    // `src` (a column of the batch, or of the domain being left) at the row ids of the batch `g`: a value column joins g's next
+    // launch; a BOOLEAN column and the validity words are bitmap gathers of their own.  n is the row count of the NEW domain.
+    Vec gathered(const Vec &src, Gather &g) {
+        Vec c;
+        c.type = src.type;
+        c.dict = src.dict;
+        if (src.type == QE_BOOLEAN) {
+            c.data = alloc_words();
+            launch_gather_bits_rows(s, words(src.data), g.ga.idx, n, words(c.data));
+        } else {
+            c.data = alloc_col(src.type);
+            g.add(src.data, c.data, (int)type_width(src.type));
+        }
+        if (src.valid) {
+            c.valid = alloc_words();
+            launch_gather_bits_rows(s, words(src.valid), g.ga.idx, n, words(c.valid));
+        }
+        return c;
+    }
+
     // column j in the current domain: gathered from the batch when a node first needs it here
     const Vec &column(int j) {
         const Vec &b = base[(size_t)j];
         if (!ids) return b;          // whole batch: the column itself (never cached: narrowing would re-gather it for nothing)
         Vec &v = env[(size_t)j];
-        if (v.data) return v;
-        v.type = b.type;
-        v.dict = b.dict;
-        if (b.type == QE_BOOLEAN) {
-            v.data = alloc_words();
-            launch_gather_bits_rows(s, (const uint64_t *)b.data.get(), (const uint32_t *)ids.get(), n, (uint64_t *)v.data.get());
-        } else {
-            v.data = alloc_col(b.type);
-            pn::GatherArgs ga{};
-            ga.idx = (const uint32_t *)ids.get();
-            ga.m = n;
-            ga.src[0] = b.data.get();
-            ga.dst[0] = v.data.get();
-            ga.width[0] = (int)type_width(b.type);
-            ga.ncols = 1;
-            pn::gather_multi(s, ga);
-        }
-        if (b.valid) {
-            v.valid = alloc_words();
-            launch_gather_bits_rows(s, (const uint64_t *)b.valid.get(), (const uint32_t *)ids.get(), n, (uint64_t *)v.valid.get());
+        if (!v.data) {
+            Gather g(s, u32(ids), n, 1);
+            v = gathered(b, g);
         }
         return v;
     }
@@ -89,83 +122,31 @@ struct Exec {
     // the value columns in `cols` that the current (narrowed) domain has not gathered yet: ONE launch, the ids are read once
     void prefetch(const std::vector<char> &cols) {
         if (!ids || n <= 0) return;
-        pn::GatherArgs ga{};
-        ga.idx = (const uint32_t *)ids.get();
-        ga.m = n;
-        auto flush = [&]() {
-            if (ga.ncols > 0) pn::gather_multi(s, ga);
-            ga.ncols = 0;
-        };
+        Gather g(s, u32(ids), n);
         for (size_t j = 0; j < env.size(); j++) {
             if (!cols[j] || env[j].data || base[j].type == QE_BOOLEAN) continue;
             if (j < through_ids.size() && through_ids[j]) continue;
-            Vec &v = env[j];
-            v.type = base[j].type;
-            v.dict = base[j].dict;
-            v.data = alloc_col(base[j].type);
-            ga.src[ga.ncols] = base[j].data.get();
-            ga.dst[ga.ncols] = v.data.get();
-            ga.width[ga.ncols] = (int)type_width(base[j].type);
-            if (++ga.ncols == 8) flush();
-            if (base[j].valid) {
-                v.valid = alloc_words();
-                launch_gather_bits_rows(s, (const uint64_t *)base[j].valid.get(), (const uint32_t *)ids.get(), n, (uint64_t *)v.valid.get());
-            }
+            env[j] = gathered(base[j], g);
         }
-        flush();
+        g.flush();
     }
 
     // narrow the domain to its rows rel[0..m) (ascending positions inside the current domain)
     void narrow(const Buf &rel, int64_t m) {
-        const uint32_t *r = (const uint32_t *)rel.get();
-        const int64_t old_n = n;
-        (void)old_n;
         n = m;
         // the row ids and every value column the old domain had gathered move to the new one in ONE launch (the positions
         // `rel` are read once)
-        pn::GatherArgs ga{};
-        ga.idx = r;
-        ga.m = m;
-        std::vector<Buf> keep_alive;
-        auto flush = [&]() {
-            if (ga.ncols > 0) pn::gather_multi(s, ga);
-            ga.ncols = 0;
-        };
+        Gather g(s, u32(rel), m);
         if (ids) {
             Buf nids = alloc((size_t)std::max<int64_t>(m, 1) * 4);
-            ga.src[ga.ncols] = ids.get();
-            ga.dst[ga.ncols] = nids.get();
-            ga.width[ga.ncols] = 4;
-            ga.ncols++;
-            keep_alive.push_back(ids);   // the old ids stay allocated until the gather has been launched
+            g.add(ids, nids, 4);
             ids = nids;
         } else {
             ids = rel;
         }
-        for (size_t j = 0; j < env.size(); j++) {
-            Vec &v = env[j];
-            if (!v.data) continue;           // never needed so far: gathered from the batch if a later node asks for it
-            Vec c;
-            c.type = v.type;
-            c.dict = v.dict;
-            if (v.type == QE_BOOLEAN) {
-                c.data = alloc_words();
-                launch_gather_bits_rows(s, (const uint64_t *)v.data.get(), r, m, (uint64_t *)c.data.get());
-            } else {
-                c.data = alloc_col(v.type);
-                ga.src[ga.ncols] = v.data.get();
-                ga.dst[ga.ncols] = c.data.get();
-                ga.width[ga.ncols] = (int)type_width(v.type);
-                keep_alive.push_back(v.data);   // the source stays allocated until its gather has been launched
-                if (++ga.ncols == 8) flush();
-            }
-            if (v.valid) {
-                c.valid = alloc_words();
-                launch_gather_bits_rows(s, (const uint64_t *)v.valid.get(), r, m, (uint64_t *)c.valid.get());
-            }
-            v = c;
-        }
-        flush();
+        for (Vec &v : env)
+            if (v.data) v = gathered(v, g);   // (never needed so far: gathered from the batch if a later node asks for it)
+        g.flush();
     }
 
     Buf alloc(size_t bytes) {
@@ -181,7 +162,7 @@ struct Exec {
         o.ptr = v.scalar ? nullptr : v.data.get();
         o.f = v.f;
         o.i = v.i;
-        o.idx = v.indexed ? (const uint32_t *)ids.get() : nullptr;
+        o.idx = v.indexed ? u32(ids) : nullptr;
         return o;
     }
 
@@ -192,7 +173,7 @@ struct Exec {
         r.scalar = false;
         if (v.type == QE_BOOLEAN) {
             r.data = alloc_words();
-            pn::word_fill(s, v.i ? ~0ull : 0ull, (uint64_t *)r.data.get(), bitmap_words(n));
+            pn::word_fill(s, v.i ? ~0ull : 0ull, words(r.data), bitmap_words(n));
         } else {
             r.data = alloc_col(v.type);
             pn::fill(s, kernel_type(v.type), opnd(v), r.data.get(), n);
@@ -204,32 +185,33 @@ struct Exec {
         if (!a) return b;
         if (!b) return a;
         Buf r = alloc_words();
-        pn::word_op(s, pn::W_AND, (const uint64_t *)a.get(), (const uint64_t *)b.get(), (uint64_t *)r.get(), bitmap_words(n));
+        pn::word_op(s, pn::W_AND, words(a), words(b), words(r), bitmap_words(n));
         return r;
     }
 
-    // map a STRING code column through a host table (string ranks, code remaps) -> INT32 column
-    std::vector<std::shared_ptr<std::vector<int32_t>>> keep_tables;   // host staging must outlive the async copies
-    Buf lookup(const std::vector<int32_t> &table, const Vec &codes) {
-        auto host = std::make_shared<std::vector<int32_t>>(table);
-        keep_tables.push_back(host);
-        Buf dev = alloc(host->size() * 4);
-        if (!host->empty()) QE_HIP(hipMemcpyAsync(dev.get(), host->data(), host->size() * 4, hipMemcpyHostToDevice, s));
-        Buf out = alloc_col(QE_INT32);
-        pn::lookup_codes(s, (const int32_t *)dev.get(), (int32_t)host->size(), (const int32_t *)codes.data.get(), (int32_t *)out.get(), n);
-        keep_dev.push_back(dev);
-        return out;
-    }
-    std::vector<Buf> keep_dev;
-
-    // a plan constant table (membership bits / hash set) on the device
+    // A host table on the device: string ranks and code remaps, membership bits and hash-set words.  The host copy must outlive
+    // the async copy and the device buffer the kernels that read it: both are held until the executor is gone.  The host copy
+    // lies in the context's pinned pool, not in malloc's memory: with a 1 MiB hash set there, an execution took 19 ms where
+    // malloc mapped the block afresh and 36 - 48 ms where it grew the heap for it and trimmed the heap again afterwards, and
+    // which of the two a process did followed from its earlier allocations (profiles/pernode_evaluator_refactor_summary.txt).
+    struct Staged { Buf host, dev; };
+    std::vector<Staged> staged;
     Buf upload(const std::vector<int32_t> &table) {
-        auto host = std::make_shared<std::vector<int32_t>>(table);
-        keep_tables.push_back(host);
-        Buf dev = alloc(std::max<size_t>(host->size() * 4, 16));
-        if (!host->empty()) QE_HIP(hipMemcpyAsync(dev.get(), host->data(), host->size() * 4, hipMemcpyHostToDevice, s));
-        keep_dev.push_back(dev);
-        return dev;
+        const size_t bytes = table.size() * 4;
+        qe_ctx *c = ctx;
+        Staged t{Buf(ctx->pinned.alloc(bytes), [c](void *q) { c->pinned.release(q); }), alloc(std::max<size_t>(bytes, 16))};
+        if (bytes > 0) {
+            std::memcpy(t.host.get(), table.data(), bytes);
+            QE_HIP(hipMemcpyAsync(t.dev.get(), t.host.get(), bytes, hipMemcpyHostToDevice, s));
+        }
+        staged.push_back(t);
+        return t.dev;
+    }
+    // a STRING code column mapped through such a table -> INT32 column
+    Buf lookup(const std::vector<int32_t> &table, const Vec &v) {
+        Buf dev = upload(table), out = alloc_col(QE_INT32);
+        pn::lookup_codes(s, codes(dev), (int32_t)table.size(), codes(v.data), codes(out), n);
+        return out;
     }
 
     // IN / LIKE: carries plan_member out.  Every route that is no constant goes through a table (a compare chain is an economy of
@@ -239,11 +221,7 @@ struct Exec {
         const Node &vn = e.nodes[nd.ops[0]];
         Vec r;
         r.type = QE_BOOLEAN;
-        int int_node = -1;
-        if (vn.kind == N_CAST && vn.type == QE_DOUBLE) {
-            const Node &c = e.nodes[vn.ops[0]];
-            if ((c.type == QE_INT64 || c.type == QE_INT32) && c.kind != N_NUM) int_node = vn.ops[0];
-        }
+        const int int_node = integer_cast_operand(e, nd.ops[0]);
         MemberPlan mp;
         Vec a;
         if (vn.type == QE_STRING && vn.kind == N_COLUMN) {   // a folded test asks the column for its validity only
@@ -272,7 +250,7 @@ struct Exec {
         case MemberPlan::Negate:
             a = materialize(a);
             r.data = alloc_words();
-            pn::word_not(s, (const uint64_t *)a.data.get(), (uint64_t *)r.data.get(), bitmap_words(n));
+            pn::word_not(s, words(a.data), words(r.data), bitmap_words(n));
             return r;
         default: break;
         }
@@ -280,7 +258,7 @@ struct Exec {
         const int kt = kernel_type(a.type);
         r.data = alloc_words();
         if (mp.kind == MemberPlan::Bits) {
-            pn::member_bits(s, kt, a.data.get(), mp.base, mp.nbits, (const uint32_t *)upload(mp.table).get(), (uint64_t *)r.data.get(), n);
+            pn::member_bits(s, kt, a.data.get(), mp.base, mp.nbits, u32(upload(mp.table)), words(r.data), n);
             return r;
         }
         if (mp.kind == MemberPlan::Chain) {   // the same members as a hash set
@@ -291,13 +269,13 @@ struct Exec {
                 mp.table.push_back((int32_t)(uint32_t)(w >> 32));
             }
         }
-        pn::member_hash(s, kt, a.data.get(), (const uint64_t *)upload(mp.table).get(), (uint64_t *)r.data.get(), n);
+        pn::member_hash(s, kt, a.data.get(), words(upload(mp.table)), words(r.data), n);
         return r;
     }
 
     Buf ones() {
         Buf r = alloc_words();
-        pn::word_fill(s, ~0ull, (uint64_t *)r.get(), bitmap_words(n));
+        pn::word_fill(s, ~0ull, words(r), bitmap_words(n));
         return r;
     }
 
@@ -333,7 +311,7 @@ struct Exec {
             if (!ids || !b.valid) return b.valid;
             if (env[(size_t)on.col].data) return env[(size_t)on.col].valid;
             Buf k = alloc_words();
-            launch_gather_bits_rows(s, (const uint64_t *)b.valid.get(), (const uint32_t *)ids.get(), n, (uint64_t *)k.get());
+            launch_gather_bits_rows(s, words(b.valid), u32(ids), n, words(k));
             return k;
         }
         return eval(e, oid).valid;
@@ -382,7 +360,7 @@ struct Exec {
                          : nd.fn == QE_FN_DIV ? pn::A_DIV : pn::A_MOD;
             if (nd.type != QE_DOUBLE && (op == pn::A_DIV || op == pn::A_MOD)) {
                 Buf nz = alloc_words();   // integer division by zero => NULL
-                pn::nonzero(s, nd.type, opnd(b), (uint64_t *)nz.get(), n);
+                pn::nonzero(s, nd.type, opnd(b), words(nz), n);
                 r.valid = and_valid(r.valid, nz);
             }
             r.data = alloc_col(nd.type);
@@ -394,19 +372,13 @@ struct Exec {
                           : nd.fn == QE_FN_CMP_GT ? pn::C_GT : nd.fn == QE_FN_CMP_EQ ? pn::C_EQ : pn::C_NE;
             const int ot = e.nodes[nd.ops[0]].type;
             if (ot == QE_DOUBLE) {
-                // (double)int_column OP integral literal that exact_integer_literal accepts: compared on the integers -- no cast
-                // kernel, no 8-byte temporary.  The compare kernel runs at the column's width: the literal must fit an INT32 column.
-                auto int_child = [&](int id) {
-                    const Node &x = e.nodes[id];
-                    if (x.kind != N_CAST || x.type != QE_DOUBLE) return -1;
-                    const Node &c = e.nodes[x.ops[0]];
-                    return ((c.type == QE_INT64 || c.type == QE_INT32) && c.kind != N_NUM) ? x.ops[0] : -1;
-                };
+                // (double)int_column OP integral literal that exact_integer_literal accepts at the column's width: compared on
+                // the integers -- no cast kernel, no 8-byte temporary
                 auto int_lit = [&](int id, int ctype, long long &v) {
                     const Node &x = e.nodes[id];
-                    return x.kind == N_NUM && exact_integer_literal(x.num, v) && (ctype == QE_INT64 || (v >= -2147483648ll && v <= 2147483647ll));
+                    return x.kind == N_NUM && exact_integer_literal(x.num, ctype, v);
                 };
-                const int ia = int_child(nd.ops[0]), ib = int_child(nd.ops[1]);
+                const int ia = integer_cast_operand(e, nd.ops[0]), ib = integer_cast_operand(e, nd.ops[1]);
                 long long lit = 0;
                 const bool left = ia >= 0 && int_lit(nd.ops[1], e.nodes[ia].type, lit);
                 const bool right = !left && ib >= 0 && int_lit(nd.ops[0], e.nodes[ib].type, lit);
@@ -418,7 +390,7 @@ struct Exec {
                         k.i = lit;
                         r.valid = col.valid;
                         r.data = alloc_words();
-                        pn::compare(s, col.type, cmp, 0, left ? opnd(col) : opnd(k), left ? opnd(k) : opnd(col), (uint64_t *)r.data.get(), n);
+                        pn::compare(s, col.type, cmp, 0, left ? opnd(col) : opnd(k), left ? opnd(k) : opnd(col), words(r.data), n);
                         return r;
                     }
                 }
@@ -439,7 +411,7 @@ struct Exec {
                     else if (sc.kind == StringCompare::Ranks) x[i]->data = lookup(sc.table[i], *x[i]);
                 }
                 r.data = alloc_words();
-                pn::compare(s, QE_INT32, cmp, 0, opnd(a), opnd(b), (uint64_t *)r.data.get(), n);
+                pn::compare(s, QE_INT32, cmp, 0, opnd(a), opnd(b), words(r.data), n);
                 return r;
             }
             if (ot == QE_BOOLEAN) {   // Boolean.compare on bitmaps: false < true
@@ -447,28 +419,28 @@ struct Exec {
                 const int w = cmp == pn::C_EQ ? pn::W_XNOR : cmp == pn::C_NE ? pn::W_XOR : cmp == pn::C_LT ? pn::W_NOTAND
                             : cmp == pn::C_LE ? pn::W_NOTOR : cmp == pn::C_GT ? pn::W_ANDNOT : pn::W_ORNOT;
                 r.data = alloc_words();
-                pn::word_op(s, w, (const uint64_t *)x.data.get(), (const uint64_t *)y.data.get(), (uint64_t *)r.data.get(), bitmap_words(n));
+                pn::word_op(s, w, words(x.data), words(y.data), words(r.data), bitmap_words(n));
                 return r;
             }
             if (a.scalar && b.scalar) a = materialize(a);
             r.data = alloc_words();
-            pn::compare(s, ot, cmp, ieee, opnd(a), opnd(b), (uint64_t *)r.data.get(), n);
+            pn::compare(s, ot, cmp, ieee, opnd(a), opnd(b), words(r.data), n);
             return r;
         }
         case QE_FN_NOT: {   // ClosureCompiler.kt:115: null -> null
             Vec a = materialize(eval(e, nd.ops[0]));
             r.valid = a.valid;
             r.data = alloc_words();
-            pn::word_not(s, (const uint64_t *)a.data.get(), (uint64_t *)r.data.get(), bitmap_words(n));
+            pn::word_not(s, words(a.data), words(r.data), bitmap_words(n));
             return r;
         }
         case QE_FN_AND: case QE_FN_OR: {
             Vec a = materialize(eval(e, nd.ops[0])), b = materialize(eval(e, nd.ops[1]));
             r.data = alloc_words();
             if (a.valid || b.valid) r.valid = alloc_words();
-            pn::kleene(s, nd.fn == QE_FN_AND, (const uint64_t *)a.data.get(), (const uint64_t *)a.valid.get(),
-                       (const uint64_t *)b.data.get(), (const uint64_t *)b.valid.get(), (uint64_t *)r.data.get(),
-                       (uint64_t *)r.valid.get(), bitmap_words(n));
+            pn::kleene(s, nd.fn == QE_FN_AND, words(a.data), words(a.valid),
+                       words(b.data), words(b.valid), words(r.data),
+                       words(r.valid), bitmap_words(n));
             return r;
         }
         case QE_FN_IF: {   // Interpreter.kt:46-53: null condition -> null; both branches evaluated, then selected
@@ -479,17 +451,17 @@ struct Exec {
             if (nd.type == QE_BOOLEAN) {
                 Vec tt = materialize(t), ff = materialize(f);
                 r.data = alloc_words();
-                pn::select_words(s, (const uint64_t *)cond.get(), (const uint64_t *)tt.data.get(), (const uint64_t *)ff.data.get(),
-                                 (uint64_t *)r.data.get(), bitmap_words(n));
+                pn::select_words(s, words(cond), words(tt.data), words(ff.data),
+                                 words(r.data), bitmap_words(n));
             } else {
                 r.data = alloc_col(nd.type);
-                pn::select(s, kernel_type(nd.type), (const uint64_t *)cond.get(), opnd(t), opnd(f), r.data.get(), n);
+                pn::select(s, kernel_type(nd.type), words(cond), opnd(t), opnd(f), r.data.get(), n);
             }
             if (t.valid || f.valid) {
                 Buf kt = t.valid ? t.valid : ones(), kf = f.valid ? f.valid : ones();
                 Buf sel = alloc_words();
-                pn::select_words(s, (const uint64_t *)cond.get(), (const uint64_t *)kt.get(), (const uint64_t *)kf.get(),
-                                 (uint64_t *)sel.get(), bitmap_words(n));
+                pn::select_words(s, words(cond), words(kt), words(kf),
+                                 words(sel), bitmap_words(n));
                 r.valid = and_valid(c.valid, sel);
             } else {
                 r.valid = c.valid;
@@ -500,8 +472,8 @@ struct Exec {
             const Buf k = validity(e, nd.ops[0]);
             const bool is_null = nd.fn == QE_FN_IS_NULL;
             r.data = alloc_words();
-            if (!k) pn::word_fill(s, is_null ? 0ull : ~0ull, (uint64_t *)r.data.get(), bitmap_words(n));
-            else if (is_null) pn::word_not(s, (const uint64_t *)k.get(), (uint64_t *)r.data.get(), bitmap_words(n));
+            if (!k) pn::word_fill(s, is_null ? 0ull : ~0ull, words(r.data), bitmap_words(n));
+            else if (is_null) pn::word_not(s, words(k), words(r.data), bitmap_words(n));
             else if (n > 0) QE_HIP(hipMemcpyAsync(r.data.get(), k.get(), bitmap_bytes(n), hipMemcpyDeviceToDevice, s));
             return r;
         }
@@ -512,15 +484,15 @@ struct Exec {
             if (nd.type == QE_BOOLEAN) {
                 Vec bb = materialize(b);
                 r.data = alloc_words();
-                pn::select_words(s, (const uint64_t *)a.valid.get(), (const uint64_t *)a.data.get(), (const uint64_t *)bb.data.get(),
-                                 (uint64_t *)r.data.get(), bitmap_words(n));
+                pn::select_words(s, words(a.valid), words(a.data), words(bb.data),
+                                 words(r.data), bitmap_words(n));
             } else {
                 r.data = alloc_col(nd.type);
-                pn::select(s, kernel_type(nd.type), (const uint64_t *)a.valid.get(), opnd(a), opnd(b), r.data.get(), n);
+                pn::select(s, kernel_type(nd.type), words(a.valid), opnd(a), opnd(b), r.data.get(), n);
             }
             if (b.valid) {
                 r.valid = alloc_words();
-                pn::word_op(s, pn::W_OR, (const uint64_t *)a.valid.get(), (const uint64_t *)b.valid.get(), (uint64_t *)r.valid.get(), bitmap_words(n));
+                pn::word_op(s, pn::W_OR, words(a.valid), words(b.valid), words(r.valid), bitmap_words(n));
             }
             return r;
         }
@@ -536,6 +508,110 @@ struct Exec {
         case QE_FN_IN: case QE_FN_LIKE: return member(e, id);
         default: fail(QE_ERR_INTERNAL, "bad function");
         }
+    }
+
+    // ---- the plan, piece by piece (run_per_node) ---------------------------------------------------------------------------
+    // Before the first launch: the plan's column errors, and which columns are read through the row ids.  A value column that
+    // the whole plan uses exactly once, as a direct operand of an arithmetic or comparison node, is never gathered into a
+    // narrowed domain: the node reads it through the row ids (cfg 2: `a + b` after the filter -- 0.8 GB less written and
+    // 0.8 GB less read per 1 B rows; cfg 3: `l_quantity < 24`, `l_extendedprice * ..`).
+    // Returns the columns whose VALUES the projections read (a null test asks for the validity only).
+    std::vector<char> analyse(const qe_batch *batch, const qe_expr *filter, const qe_expr *const *projs, int32_t nproj) {
+        std::vector<char> proj_values(env.size(), 0);
+        std::vector<int> col_types, refs(env.size(), 0), direct(env.size(), 0);
+        std::vector<std::shared_ptr<DictData>> dicts;
+        for (const Column &c : batch->cols) {
+            col_types.push_back(c.type);
+            dicts.push_back(c.dict);
+        }
+        auto scan = [&](const Expr &pe, bool projection) {
+            const std::vector<char> folded = constant_column_members(pe, dicts);   // an IN / LIKE folded to a constant reads the validity only
+            for (const ColumnUse &u : column_uses(pe, pe.root, col_types, &folded)) {   // (raises the plan's column errors before the first launch)
+                refs[(size_t)u.col]++;
+                if (projection && u.value) proj_values[(size_t)u.col] = 1;
+            }
+            for (const Node &nd : pe.nodes)
+                if (nd.kind == N_FN && (is_arithmetic_fn(nd.fn) || is_comparison_fn(nd.fn)))
+                    for (int op : nd.ops)
+                        if (pe.nodes[(size_t)op].kind == N_COLUMN) direct[(size_t)pe.nodes[(size_t)op].col]++;
+        };
+        if (filter) scan(filter->e, false);
+        for (int32_t i = 0; i < nproj; i++) {
+            if (!projs[i]) fail(QE_ERR_INVALID_ARG, "null projection");
+            scan(projs[i]->e, true);
+        }
+        through_ids.assign(env.size(), 0);
+        for (size_t j = 0; j < env.size(); j++)
+            through_ids[j] = refs[j] == 1 && direct[j] == 1 && !base[j].valid &&
+                             (base[j].type == QE_DOUBLE || base[j].type == QE_INT64 || base[j].type == QE_INT32);
+        return proj_values;
+    }
+
+    // Steps 1 - 3 of the file comment: the filter, conjunct by conjunct, leaves the domain at the kept rows
+    void filter_domain(const Expr &fe, const std::vector<char> &proj_values) {
+        if (fe.nodes[fe.root].type != QE_BOOLEAN) fail(QE_ERR_PROGRAM, "filter expression must be BOOLEAN");
+        const std::vector<int> conj = split_conjuncts(fe, fe.root);   // 1. the top-level AND chain, left to right
+        unsigned long long *d_total = (unsigned long long *)(ctx->d_ctrl + 2);
+        Buf acc;   // keep mask accumulated over the conjuncts evaluated in the current domain since it was last narrowed
+        for (size_t ci = 0; ci < conj.size() && n > 0; ci++) {
+            const bool last = ci + 1 == conj.size();
+            Vec k = materialize(eval(fe, conj[ci]));
+            Buf keep = and_valid(k.data, k.valid);              // value & known (FilterOperator.kt:20)
+            acc = and_valid(acc, keep);
+            // 2. kept rows of the current domain
+            const int64_t nw = bitmap_words(n);
+            Buf offsets = alloc((size_t)(nw + 1) * 4), sums = alloc((size_t)scan_blocks(nw + 1) * 4);
+            bitmap_ranks(s, words(acc), nullptr, n, u32(offsets), u32(sums), d_total);
+            QE_HIP(hipMemcpyAsync(ctx->h_ctrl, ctx->d_ctrl, 16, hipMemcpyDeviceToHost, s));
+            QE_HIP(hipGetLastError());
+            QE_HIP(hipStreamSynchronize(s));
+            const int64_t kept = (int64_t)ctx->h_ctrl[1];
+            if (last && ctx->opts.result_capacity_rows > 0 && kept > ctx->opts.result_capacity_rows)   // same contract as the fused path
+                fail(QE_ERR_INVALID_ARG, "result has " + std::to_string(kept) + " rows but result_capacity_rows is " +
+                                             std::to_string(ctx->opts.result_capacity_rows));
+            if (kept == n) { acc.reset(); continue; }           // everything survived: the domain stays as it is
+            if (!last && kept * 2 > n) continue;                // not selective enough to pay for a compaction yet: keep the mask
+            Buf rel = alloc((size_t)std::max<int64_t>(kept, 1) * 4);
+            bitmap_positions(s, words(acc), nullptr, n, u32(offsets), u32(rel), kept, false);
+            narrow(rel, kept);
+            acc.reset();
+        }
+        // 3. the projections' columns that the final domain has not seen yet: one gather launch
+        prefetch(proj_values);
+    }
+
+    // Step 4: one projection over the final domain, as a column of the result (which shares the buffer with the executor's
+    // temporaries: hold_data / hold_valid)
+    OutColumn project(const Expr &pe, const qe_batch *batch) {
+        Vec v = eval(pe, pe.root);
+        if (v.is_str_lit) {   // SELECT 'lit'
+            v.dict = literal_dictionary(v.lit);
+            v.i = 0;
+            v.is_str_lit = false;
+        }
+        OutColumn oc;
+        oc.type = v.type;
+        oc.dict = v.dict;
+        oc.dict_handle.d = v.dict;
+        oc.nullable = (bool)v.valid;
+        if (n <= 0) return oc;
+        v = materialize(v);
+        // a bare column of an unfiltered batch aliases the caller's input: the result must own its data
+        auto owned = [&](const Buf &b, size_t bytes) -> Buf {
+            if (!b) return b;
+            for (const Column &c : batch->cols)
+                if (b.get() == c.data || b.get() == (void *)c.validity) {
+                    Buf copy = alloc(bytes);
+                    QE_HIP(hipMemcpyAsync(copy.get(), b.get(), bytes, hipMemcpyDeviceToDevice, s));
+                    return copy;
+                }
+            return b;
+        };
+        oc.hold_data = owned(v.data, column_bytes(v.type, n));
+        oc.hold_valid = owned(v.valid, bitmap_bytes(n));
+        oc.data = oc.hold_data.get();
+        oc.validity = words(oc.hold_valid);
+        return oc;
     }
 };
 
@@ -562,119 +638,17 @@ qe_result *run_per_node(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filte
         e.dict = c.dict;
         x.env.push_back(e);          // not gathered yet
     }
-    ResultPtr res = new_result(ctx, 0);   // (its columns share their buffers with the executor's temporaries: hold_data / hold_valid)
-    int64_t m = batch->nrows;
-    // A value column that the whole plan uses exactly once, as a direct operand of an arithmetic or comparison node, is never
-    // gathered into a narrowed domain: the node reads it through the row ids (cfg 2: `a + b` after the filter -- 0.8 GB less
-    // written and 0.8 GB less read per 1 B rows; cfg 3: `l_quantity < 24`, `l_extendedprice * ..`).
-    std::vector<char> proj_values(x.env.size(), 0);   // columns whose VALUES the projections read (a null test asks for the validity only)
-    {
-        std::vector<int> col_types, refs(x.env.size(), 0), direct(x.env.size(), 0);
-        for (const Column &c : batch->cols) col_types.push_back(c.type);
-        auto scan = [&](const Expr &pe, bool projection) {
-            std::vector<std::shared_ptr<DictData>> dicts;
-            for (const Column &c : batch->cols) dicts.push_back(c.dict);
-            const std::vector<char> folded = constant_column_members(pe, dicts);   // an IN / LIKE folded to a constant reads the validity only
-            for (const ColumnUse &u : column_uses(pe, pe.root, col_types, &folded)) {   // (raises the plan's column errors before the first launch)
-                refs[(size_t)u.col]++;
-                if (projection && u.value) proj_values[(size_t)u.col] = 1;
-            }
-            for (const Node &nd : pe.nodes)
-                if (nd.kind == N_FN && (is_arithmetic_fn(nd.fn) || is_comparison_fn(nd.fn)))
-                    for (int op : nd.ops)
-                        if (pe.nodes[(size_t)op].kind == N_COLUMN) direct[(size_t)pe.nodes[(size_t)op].col]++;
-        };
-        if (filter) scan(filter->e, false);
-        for (int32_t i = 0; i < nproj; i++) {
-            if (!projs[i]) fail(QE_ERR_INVALID_ARG, "null projection");
-            scan(projs[i]->e, true);
-        }
-        x.through_ids.assign(x.env.size(), 0);
-        for (size_t j = 0; j < x.env.size(); j++)
-            x.through_ids[j] = refs[j] == 1 && direct[j] == 1 && !x.base[j].valid &&
-                               (x.base[j].type == QE_DOUBLE || x.base[j].type == QE_INT64 || x.base[j].type == QE_INT32);
-    }
+    ResultPtr res = new_result(ctx, 0);
+    const std::vector<char> proj_values = x.analyse(batch, filter, projs, nproj);
     if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-    if (filter && batch->nrows > 0) {
-        const Expr &fe = filter->e;
-        if (fe.nodes[fe.root].type != QE_BOOLEAN) fail(QE_ERR_PROGRAM, "filter expression must be BOOLEAN");
-        const std::vector<int> conj = split_conjuncts(fe, fe.root);   // 1. the top-level AND chain, left to right
-        unsigned long long *d_total = (unsigned long long *)(ctx->d_ctrl + 2);
-        Buf acc;   // keep mask accumulated over the conjuncts evaluated in the current domain since it was last narrowed
-        for (size_t ci = 0; ci < conj.size() && x.n > 0; ci++) {
-            const bool last = ci + 1 == conj.size();
-            Vec k = x.materialize(x.eval(fe, conj[ci]));
-            Buf keep = x.and_valid(k.data, k.valid);              // value & known (FilterOperator.kt:20)
-            acc = x.and_valid(acc, keep);
-            // 2. kept rows of the current domain
-            const int64_t nw = bitmap_words(x.n);
-            Buf offsets = x.alloc((size_t)(nw + 1) * 4), sums = x.alloc((size_t)scan_blocks(nw + 1) * 4);
-            bitmap_ranks(x.s, (const uint64_t *)acc.get(), nullptr, x.n, (uint32_t *)offsets.get(), (uint32_t *)sums.get(), d_total);
-            QE_HIP(hipMemcpyAsync(ctx->h_ctrl, ctx->d_ctrl, 16, hipMemcpyDeviceToHost, x.s));
-            QE_HIP(hipGetLastError());
-            QE_HIP(hipStreamSynchronize(x.s));
-            const int64_t kept = (int64_t)ctx->h_ctrl[1];
-            if (last && ctx->opts.result_capacity_rows > 0 && kept > ctx->opts.result_capacity_rows)   // same contract as the fused path
-                fail(QE_ERR_INVALID_ARG, "result has " + std::to_string(kept) + " rows but result_capacity_rows is " +
-                                             std::to_string(ctx->opts.result_capacity_rows));
-            if (kept == x.n) { acc.reset(); continue; }           // everything survived: the domain stays as it is
-            if (!last && kept * 2 > x.n) continue;                // not selective enough to pay for a compaction yet: keep the mask
-            Buf rel = x.alloc((size_t)std::max<int64_t>(kept, 1) * 4);
-            bitmap_positions(x.s, (const uint64_t *)acc.get(), nullptr, x.n, (const uint32_t *)offsets.get(), (uint32_t *)rel.get(), kept, false);
-            x.narrow(rel, kept);
-            acc.reset();
-        }
-        m = x.n;
-        // 3. the projections' columns that the final domain has not seen yet: one gather launch
-        x.prefetch(proj_values);
-    }
-    // 4. projections over the (compacted) domain
-    res->count = m;
-    res->capacity = m;
-    for (int32_t i = 0; i < nproj; i++) {
-        const Expr &pe = projs[i]->e;
-        Vec v = x.eval(pe, pe.root);
-        if (v.is_str_lit) {   // SELECT 'lit'
-            v.dict = literal_dictionary(v.lit);
-            v.i = 0;
-            v.is_str_lit = false;
-        }
-        if (m > 0) v = x.materialize(v);
-        OutColumn oc;
-        oc.type = v.type;
-        oc.dict = v.dict;
-        oc.dict_handle.d = v.dict;
-        oc.nullable = (bool)v.valid;
-        if (m > 0) {
-            // a bare column of an unfiltered batch aliases the caller's input: the result must own its data
-            auto owned = [&](const Buf &b, size_t bytes) -> Buf {
-                if (!b) return b;
-                for (const Column &c : batch->cols)
-                    if (b.get() == c.data || b.get() == (void *)c.validity) {
-                        Buf copy = x.alloc(bytes);
-                        QE_HIP(hipMemcpyAsync(copy.get(), b.get(), bytes, hipMemcpyDeviceToDevice, x.s));
-                        return copy;
-                    }
-                return b;
-            };
-            const size_t dbytes = column_bytes(v.type, m);
-            oc.hold_data = owned(v.data, dbytes);
-            oc.hold_valid = owned(v.valid, bitmap_bytes(m));
-            oc.data = oc.hold_data.get();
-            oc.validity = (uint64_t *)oc.hold_valid.get();
-        }
-        res->cols.push_back(oc);
-    }
+    if (filter && batch->nrows > 0) x.filter_domain(filter->e, proj_values);
+    res->count = x.n;
+    res->capacity = x.n;
+    for (int32_t i = 0; i < nproj; i++) res->cols.push_back(x.project(projs[i]->e, batch));
     if (ctx->opts.profile) QE_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(x.s));
-    if (ctx->opts.profile) {
-        float ms = 0.f;
-        QE_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        ctx->last_ms = ms;
-        ctx->total_ms += ms;
-        ctx->launches++;
-    }
+    collect_time(ctx);   // (the bracket ev0 .. ev1, when profiling)
     return res.release();
 }
 

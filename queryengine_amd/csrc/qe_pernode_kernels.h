@@ -8,7 +8,7 @@ namespace pn {
 
 enum Arith { A_ADD = 0, A_SUB, A_MUL, A_DIV, A_MOD };
 enum Cmp { C_LT = 0, C_LE, C_GE, C_GT, C_EQ, C_NE };
-enum Unary { U_ABS = 0, U_FLOOR, U_CEIL };
+enum Unary { U_ABS = 0, U_FLOOR, U_CEIL, U_NEG };
 enum WordOp { W_AND = 0, W_OR, W_XOR, W_ANDNOT /* a & ~b */, W_ORNOT /* a | ~b */, W_XNOR, W_NOTAND /* ~a & b */, W_NOTOR /* ~a | b */ };
 
 // operand: column pointer, or (ptr == nullptr) a scalar broadcast from an SGPR
@@ -23,9 +23,9 @@ struct Opnd {
 
 // type codes follow QE_* (QE_DOUBLE=1, QE_INT64=3, QE_INT32=4; STRING codes are handled as INT32)
 void arith(hipStream_t s, int type, int op, Opnd a, Opnd b, void *out, int64_t n);
-void negate(hipStream_t s, int type, const void *a, void *out, int64_t n);
-// ABS / FLOOR / CEIL, elementwise, result of the operand's type (FLOOR / CEIL of an integer column is the identity)
+// ABS / FLOOR / CEIL / unary minus, elementwise, result of the operand's type (FLOOR / CEIL of an integer column is the identity)
 void unary(hipStream_t s, int type, int op, const void *a, void *out, int64_t n);
+inline void negate(hipStream_t s, int type, const void *a, void *out, int64_t n) { unary(s, type, U_NEG, a, out, n); }
 void cast(hipStream_t s, int from, int to, const void *a, void *out, int64_t n);
 void fill(hipStream_t s, int type, Opnd v, void *out, int64_t n);
 // comparison -> value bitmap (one __ballot per 64 rows); bits of rows >= n are 0

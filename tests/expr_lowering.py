@@ -59,8 +59,10 @@ def np_coalesce(a: Column, b: Column, t: DataType) -> Column:
     va, vb = _valid(a), _valid(b)
     valid = va | vb
     if t == S:
-        sa, sb = a.to_list(), b.to_list()
-        return Column.from_values(S, [x if k else y for x, y, k in zip(sa, sb, va)])
+        # one dictionary: a's entries, then b's new ones; b's codes are renumbered into it (codes under a NULL read as 0)
+        dictionary = list(a.dictionary) + [s for s in b.dictionary if s not in a.dictionary]
+        renumber = np.array([dictionary.index(s) for s in b.dictionary] + [0], dtype=np.int32)
+        return Column(S, np.where(va, a.data, renumber[np.where(vb, b.data, len(b.dictionary))]), valid, dictionary)
     if t == B:
         return Column(B, np.where(va, a.data, b.data), valid)
     return Column(t, np.where(va, a.data.astype(_NP[t]), b.data.astype(_NP[t])), valid)

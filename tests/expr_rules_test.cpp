@@ -29,6 +29,18 @@ static int fn(Expr &e, int f, int type, std::vector<int> ops) {
     e.nodes.push_back(n);
     return e.root = (int)e.nodes.size() - 1;
 }
+static int number(Expr &e, double v, int type = QE_DOUBLE) {
+    Node n;
+    n.kind = N_NUM; n.num = v; n.type = type;
+    e.nodes.push_back(n);
+    return e.root = (int)e.nodes.size() - 1;
+}
+static int cast(Expr &e, int type, int op) {
+    Node n;
+    n.kind = N_CAST; n.type = type; n.ops = {op};
+    e.nodes.push_back(n);
+    return e.root = (int)e.nodes.size() - 1;
+}
 static std::shared_ptr<DictData> dict_of(const std::vector<std::string> &entries) {
     auto d = std::make_shared<DictData>();
     for (const std::string &s : entries) {
@@ -249,6 +261,39 @@ static void test_exact_integer_literal() {
     CHECK(exact_integer_literal(-0.0, v) && v == 0);
     CHECK(exact_integer_literal(7.0, v) && v == 7);
     CHECK(exact_integer_literal(-2147483649.0, v) && v == -2147483649ll);
+    // .. at the width of the integer operand: the INT32 bounds
+    CHECK(exact_integer_literal(2147483647.0, QE_INT32, v) && v == 2147483647ll);
+    CHECK(exact_integer_literal(-2147483648.0, QE_INT32, v) && v == -2147483648ll);
+    CHECK(!exact_integer_literal(2147483648.0, QE_INT32, v) && !exact_integer_literal(-2147483649.0, QE_INT32, v));
+    CHECK(exact_integer_literal(2147483648.0, QE_INT64, v) && v == 2147483648ll);
+    CHECK(exact_integer_literal(-2147483649.0, QE_INT64, v) && v == -2147483649ll);
+    CHECK(exact_integer_literal(two53 - 1, QE_INT64, v) && v == 9007199254740991ll && !exact_integer_literal(two53 - 1, QE_INT32, v));
+    CHECK(!exact_integer_literal(two53, QE_INT64, v) && !exact_integer_literal(-two53, QE_INT64, v));   // +-2^53: strict at every width
+    CHECK(!exact_integer_literal(two53, QE_INT32, v) && !exact_integer_literal(-two53, QE_INT32, v));
+    CHECK(!exact_integer_literal(0.5, QE_INT64, v) && !exact_integer_literal(0.5, QE_INT32, v));
+    CHECK(exact_integer_literal(-0.0, QE_INT32, v) && v == 0);
+    CHECK(!exact_integer_literal(7.0, QE_DOUBLE, v) && !exact_integer_literal(7.0, -1, v));   // no integer operand: no width
+}
+
+static void test_integer_cast_operand() {
+    Expr e;
+    const int l = column(e, 0, QE_INT64), i = column(e, 1, QE_INT32), d = column(e, 2, QE_DOUBLE), p = column(e, 3, QE_BOOLEAN);
+    const int dl = cast(e, QE_DOUBLE, l), di = cast(e, QE_DOUBLE, i);
+    CHECK(integer_cast_operand(e, dl) == l && integer_cast_operand(e, di) == i);
+    CHECK(integer_cast_operand(e, l) == -1 && integer_cast_operand(e, i) == -1 && integer_cast_operand(e, d) == -1);   // no cast
+    const int sum = fn(e, QE_FN_ADD, QE_INT64, {l, cast(e, QE_INT64, i)});
+    CHECK(integer_cast_operand(e, sum) == -1);
+    CHECK(integer_cast_operand(e, cast(e, QE_DOUBLE, sum)) == sum);                      // any integer expression, not only a column
+    const int li = cast(e, QE_INT64, i);
+    CHECK(integer_cast_operand(e, li) == -1);                                            // a cast, but not to DOUBLE
+    const int dli = cast(e, QE_DOUBLE, li);
+    CHECK(integer_cast_operand(e, dli) == li);                                           // a cast of a cast: the inner cast, not the column
+    CHECK(integer_cast_operand(e, cast(e, QE_DOUBLE, dl)) == -1);                        // (double)(double)l: the operand is a DOUBLE
+    CHECK(integer_cast_operand(e, cast(e, QE_DOUBLE, d)) == -1 && integer_cast_operand(e, cast(e, QE_DOUBLE, p)) == -1);
+    const int seven = number(e, 7.0);
+    CHECK(integer_cast_operand(e, seven) == -1 && integer_cast_operand(e, cast(e, QE_DOUBLE, seven)) == -1);   // a literal child
+    CHECK(integer_cast_operand(e, cast(e, QE_DOUBLE, number(e, 7.0, QE_INT64))) == -1);  // .. whatever type it claims
+    CHECK(integer_cast_operand(e, cast(e, QE_DOUBLE, number(e, 7.0, QE_INT32))) == -1);
 }
 
 int main() {
@@ -258,6 +303,7 @@ int main() {
     test_string_compare();
     test_dictionary_union();
     test_exact_integer_literal();
+    test_integer_cast_operand();
     if (failures) {
         std::printf("%d checks failed\n", failures);
         return 1;

@@ -51,9 +51,11 @@ def assert_columns_equal(got: Column, want: Column, what: str = "") -> None:
     bad = np.nonzero(gv != wv)[0]
     assert bad.size == 0, f"{what}: validity differs at rows {bad[:8]} (got {gv[bad[:8]]})"
     if got.type == S:
-        g = [got.dictionary[c] if v else None for c, v in zip(got.data, gv)]
-        w = [want.dictionary[c] if v else None for c, v in zip(want.data, wv)]
-        assert g == w, f"{what}: strings differ"
+        # the strings of the valid rows (the null positions are equal already), looked up as arrays: the same comparison as
+        # row by row, fast enough for columns of millions of rows
+        g = np.array(got.dictionary or [], dtype=object)[got.data[gv]]
+        w = np.array(want.dictionary or [], dtype=object)[want.data[wv]]
+        assert np.array_equal(g, w), f"{what}: strings differ"
         return
     g, w = got.data[gv], want.data[wv]
     if got.type == D:

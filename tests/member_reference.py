@@ -104,14 +104,13 @@ def like_matches(pattern: str, s: str) -> bool:
 
 def np_like(value: Column, pattern: str) -> Column:
     rx = like_regex(pattern)
-    seen = {}
+    member = np.array([rx.fullmatch(s) is not None for s in value.dictionary], dtype=bool)   # one match per entry
+    codes = value.data.astype(np.int64)
+    ok = (codes >= 0) & (codes < len(member))                   # (under a NULL anything may stand)
+    if value.valid is not None:
+        ok &= value.valid
     data = np.zeros(len(value), dtype=bool)
-    for i, s in enumerate(value.to_list()):
-        if s is None:
-            continue
-        if s not in seen:
-            seen[s] = rx.fullmatch(s) is not None
-        data[i] = seen[s]
+    data[ok] = member[codes[ok]] if len(member) else False
     return Column(B, data, value.valid)
 
 
