@@ -570,6 +570,65 @@ int32_t qe_result_group_ordered(qe_ctx *ctx, const qe_result *result,
  * passes of those sorts */
 int32_t qe_ctx_last_ordered_stats(const qe_ctx *ctx, int64_t out[4]);
 
+/* ---- set operations over two results ---------------------------------------------------------------------------
+ * UNION, INTERSECT and EXCEPT of two results, each with its ALL form, without copying either to the host.  The reference has
+ * none of them (Query.g4 reads one table).  A SEMI / ANTI join comes close to INTERSECT / EXCEPT but stops at four key columns,
+ * never matches a NULL, keeps duplicates and cannot express the multiset forms.
+ *
+ * Schema: both sides have the same number of columns (at least one) and column i has the same type on both sides; all five
+ * types are allowed and nothing is promoted.  An output column is nullable exactly when the column is nullable on either side,
+ * for every op, so the output schema follows from the inputs' schemas alone.  `left` and `right` may be the same handle.
+ *
+ * Equality of two rows is the rule by which two rows share a group in qe_result_group_ordered, on every column: NULL is a
+ * value and equals NULL, every NaN is one value, -0.0 is not 0.0, STRING compares by string, never by code.
+ *
+ * Dictionaries of STRING columns: if both sides carry the same dictionary object the output carries it too and no code
+ * changes.  Otherwise the output carries a merged dictionary: the left dictionary's entries first, in their order, so left
+ * codes are unchanged; after them the right dictionary's entries that the left does not hold, in the right dictionary's order
+ * (an entry the right dictionary lists twice is appended twice and both codes stay apart).  Right codes are translated on the
+ * device; a right entry that the left holds maps to the code the left dictionary finds for it (its first, if the left lists
+ * the string twice).  A right code outside its dictionary becomes 0.
+ *
+ * Rows kept.  For a tuple that occurs cL times on the left and cR times on the right:
+ *                   all == 0                            all == 1
+ *   QE_SET_UNION      1                                   cL + cR
+ *   QE_SET_INTERSECT  1 if cL > 0 and cR > 0, else 0      min(cL, cR)
+ *   QE_SET_EXCEPT     1 if cL > 0 and cR == 0, else 0     max(cL - cR, 0)
+ *
+ * Order: UNION ALL returns the left rows in their order, then the right rows in theirs, and runs no sort.  Every other form
+ * returns its rows ASCENDING by column 0, then column 1, and so on, under the comparator of qe_result_order_by_keys (NULL
+ * first): the order of qe_result_group_ordered.  The k copies of a tuple are its first k rows in the sequence "left rows in
+ * input order, then right rows in input order"; that fixes which NaN payload, and which of two codes of a twice-listed string,
+ * comes out, and a kept row is a left row whenever the tuple occurs on the left.  The value under a NULL is that row's.
+ *
+ * Determinism: the same inputs give the same bytes on every run and every context.  No atomic feeds a result byte (the one
+ * atomic is the integer count of tuples of the boundary flags, whose result does not depend on the order of arrival).
+ *
+ * Limits and errors (*out = NULL): QE_ERR_INVALID_ARG for a null pointer, op outside 0..2, all other than 0 or 1, different
+ * column counts, a column whose types differ, zero columns, a STRING column without a dictionary; QE_ERR_UNSUPPORTED for more
+ * than 8 columns in a form that sorts (the sort has 8 keys), more than 16 columns in UNION ALL (the limit of
+ * qe_result_concat), left rows + right rows >= 2^32 - 1; QE_ERR_HIP on a planning-only context; QE_ERR_OOM when scratch or
+ * output does not fit.
+ *
+ * Zero rows on one side or on both is an ordinary input; the output then may have zero rows and carries the full schema.
+ *
+ * Lifetime and reuse: the output owns its buffers and shares the dictionaries; both inputs may be freed once the call returns.
+ * The output is an ordinary result: qe_result_order_by_keys, qe_batch_from_result, qe_result_to_host, qe_result_concat,
+ * qe_gather, the join, the window and another set operation all take it.
+ *
+ * How: the two sides are concatenated with the placement code of qe_result_concat (right STRING codes through the translation
+ * table); one stable sort over every column; the boundary flags of the window operator mark the tuple starts; a bitmap of the
+ * sorted positions that hold a left row and its word ranks give cL and cR of every tuple in two lookups, and one pass over the
+ * sorted positions, with fixed work per row, writes the keep bitmap; its set positions go through the sort's row ids into the
+ * row gather every operator uses.  UNION with all == 0 keeps exactly the tuple starts. */
+enum { QE_SET_UNION = 0, QE_SET_INTERSECT = 1, QE_SET_EXCEPT = 2 };
+int32_t qe_result_set_op(qe_ctx *ctx, const qe_result *left, const qe_result *right,
+                         int32_t op, int32_t all, qe_result **out);
+/* what the last qe_result_set_op of this context did: out[0] left rows, out[1] right rows, out[2] distinct tuples of
+ * the two sides together found by the sort (0 for UNION ALL: no sort), out[3] STRING columns whose right-side codes were translated
+ * into a merged dictionary */
+int32_t qe_ctx_last_set_stats(const qe_ctx *ctx, int64_t out[4]);
+
 /* zero-copy: a batch whose columns ARE the result's (not owned; the result must outlive the batch).  Same columns, same
  * validity (NULL where the result has none), same dictionaries, nrows = the result's count (zero rows: a zero-row batch).
  * The batch goes into qe_filter_project / qe_filter_aggregate / qe_filter_groupby like any other: that is how a join is

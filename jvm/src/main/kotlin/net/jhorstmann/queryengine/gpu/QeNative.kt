@@ -73,6 +73,11 @@ internal object QeNative {
     // (ROWS BETWEEN preceding PRECEDING AND following FOLLOWING, -1 = UNBOUNDED; fn 10 / 11 = FIRST_VALUE / LAST_VALUE), qe_result **out
     val qe_result_window_frames = handle("qe_result_window_frames", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS)
     val qe_ctx_last_window_stats = handle("qe_ctx_last_window_stats", JAVA_INT, ADDRESS, ADDRESS)     // ctx, long[4]
+    // ---- set operations over two results of one schema: op 0 UNION, 1 INTERSECT, 2 EXCEPT; all 0 / 1 (the multiset form) ----
+    // ctx, left, right, op, all, qe_result** -> status: NULL equals NULL, strings compare by string (the sides may carry different
+    // dictionaries); UNION ALL is left's rows then right's, every other form ascending by all columns
+    val qe_result_set_op = handle("qe_result_set_op", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, ADDRESS)
+    val qe_ctx_last_set_stats = handle("qe_ctx_last_set_stats", JAVA_INT, ADDRESS, ADDRESS)           // ctx, long[4]
     // ctx, result, qe_batch** -> status: a batch whose columns ARE the result's (zero copy): the input of the next plan
     val qe_batch_from_result = handle("qe_batch_from_result", JAVA_INT, ADDRESS, ADDRESS, ADDRESS)
 

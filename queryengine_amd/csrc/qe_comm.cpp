@@ -147,7 +147,7 @@ struct RcclGroup {
 
 // The output result of a concatenation / gather: per column a values buffer for `total` rows and, if any part carries a
 // validity bitmap, a validity bitmap (parts without one contribute ones).  Bitmaps are zeroed: bitmap_place ORs segments in.
-static ResultPtr make_output(qe_ctx *ctx, const qe_result *like, int64_t total, uint32_t any_validity) {
+ResultPtr concat_output(qe_ctx *ctx, const qe_result *like, int64_t total, uint32_t any_validity) {
     ResultPtr out = new_result(ctx, total);
     for (size_t c = 0; c < like->cols.size(); c++) {
         const OutColumn &src = like->cols[c];
@@ -163,6 +163,26 @@ static uint64_t *ones_bitmap(qe_ctx *ctx, PoolScratch &sc, int64_t n) {
     uint64_t *p = (uint64_t *)sc.alloc(bitmap_bytes(n));
     QE_HIP(hipMemsetAsync(p, 0xff, bitmap_bytes(n), ctx->stream));
     return p;
+}
+
+// The rows of `part` at row offset `off` of a concat_output: values at their offset, bitmaps shifted into place, a missing
+// validity bitmap as ones.  Bit c of skip_values: the caller writes the values of column c itself (the set operation's
+// translated STRING codes); the validity is placed all the same.
+void concat_place(qe_ctx *ctx, PoolScratch &sc, const qe_result *part, int64_t off, qe_result *out, uint32_t skip_values) {
+    const int64_t n = part->count;
+    if (n == 0) return;
+    for (size_t c = 0; c < out->cols.size(); c++) {
+        const OutColumn &src = part->cols[c];
+        OutColumn &dst = out->cols[c];
+        const bool values = !((skip_values >> c) & 1u);
+        if (values && src.type == QE_BOOLEAN)
+            launch_bitmap_place(ctx->stream, (uint64_t *)dst.data, off, (const uint64_t *)src.data, n);
+        else if (values)
+            QE_HIP(hipMemcpyAsync((char *)dst.data + type_width(src.type) * (size_t)off, src.data, type_width(src.type) * (size_t)n,
+                                  hipMemcpyDeviceToDevice, ctx->stream));
+        if (dst.nullable)
+            launch_bitmap_place(ctx->stream, dst.validity, off, src.validity ? src.validity : ones_bitmap(ctx, sc, n), n);
+    }
 }
 
 }  // namespace qe
@@ -240,23 +260,11 @@ int32_t qe_result_concat(qe_ctx *ctx, const qe_result *const *parts, int32_t npa
             any_validity |= h.validity_mask;
         }
         PoolScratch sc(ctx);
-        ResultPtr res = make_output(ctx, parts[0], total, any_validity);
+        ResultPtr res = concat_output(ctx, parts[0], total, any_validity);
         int64_t off = 0;
         for (int32_t i = 0; i < nparts; i++) {
-            const int64_t n = parts[i]->count;
-            if (n == 0) continue;
-            for (size_t c = 0; c < res->cols.size(); c++) {
-                const OutColumn &src = parts[i]->cols[c];
-                OutColumn &dst = res->cols[c];
-                if (src.type == QE_BOOLEAN)
-                    launch_bitmap_place(ctx->stream, (uint64_t *)dst.data, off, (const uint64_t *)src.data, n);
-                else
-                    QE_HIP(hipMemcpyAsync((char *)dst.data + type_width(src.type) * (size_t)off, src.data, type_width(src.type) * (size_t)n,
-                                          hipMemcpyDeviceToDevice, ctx->stream));
-                if (dst.nullable)
-                    launch_bitmap_place(ctx->stream, dst.validity, off, src.validity ? src.validity : ones_bitmap(ctx, sc, n), n);
-            }
-            off += n;
+            concat_place(ctx, sc, parts[i], off, res.get(), 0);
+            off += parts[i]->count;
         }
         QE_HIP(hipGetLastError());
         QE_HIP(hipStreamSynchronize(ctx->stream));
@@ -336,7 +344,7 @@ int32_t qe_gather(qe_ctx *ctx, const qe_result *local, int32_t root, qe_result *
                 }
             }
             if (rank == root) {
-                res = make_output(ctx, local, total, any_validity);
+                res = concat_output(ctx, local, total, any_validity);
                 for (int r = 0; r < nranks; r++) {
                     const int64_t n = hdr[r].count;
                     if (n == 0 || r == root) continue;
@@ -510,7 +518,7 @@ int32_t qe_filter_project_gather(qe_ctx *ctx, const qe_batch *batch, const qe_ex
                 ones = w;
             }
             if (rank == root) {
-                res = make_output(ctx, probe.get(), total, any_validity);
+                res = concat_output(ctx, probe.get(), total, any_validity);
                 for (int k = 0; k < max_slices; k++) {
                     for (int r = 0; r < nranks; r++) {
                         if (r == root || k >= hdr[r].nslices || hdr[r].count[k] == 0) continue;

@@ -13,6 +13,8 @@
 //   qe_window.cpp    window functions over a result: the sort, the boundary flags, the segmented scans
 //   qe_ordered.cpp   ordered-set aggregates per group (quantiles, COUNT DISTINCT, MODE): one sort per argument column, the
 //                    window's boundary flags, then ranks, compaction and picks over the sorted rows
+//   qe_setop.cpp     UNION / INTERSECT / EXCEPT [ALL] of two results: the concatenation, one sort over every column, the
+//                    boundary flags, a keep bitmap from per-tuple counts of the two sides, the row gather
 #pragma once
 
 #include <memory>
@@ -122,6 +124,13 @@ struct SortDriver {
     // stable sort of the row ids in side 0 of `rb` (identity: they are 0..m-1 and are written here) by all keys
     void sort(RadixBuffers &rb, bool identity);
 };
+
+// ---- qe_comm.cpp: the placement code behind qe_result_concat / qe_gather, shared with the set operations -------------------
+// A result of `total` rows with the column types and dictionaries of `like`; bit c of any_validity: column c carries a
+// validity bitmap.  BOOLEAN values and validity are zeroed: concat_place ORs segments in.
+ResultPtr concat_output(qe_ctx *ctx, const qe_result *like, int64_t total, uint32_t any_validity);
+// the rows of `part` at row offset `off` of such a result (bit c of skip_values: the caller writes column c's values itself)
+void concat_place(qe_ctx *ctx, PoolScratch &sc, const qe_result *part, int64_t off, qe_result *out, uint32_t skip_values);
 
 // ---- qe_api.cpp: plans and launches -------------------------------------------------------------------------
 // What get_plan is asked for; a call site names only what it sets.

@@ -438,6 +438,7 @@ struct qe_ctx {
     int64_t join_stats[4] = {0, 0, 0, 0};   // qe_ctx_last_join_stats: build rows in the table, probe rows, output rows, longest run walked
     int64_t window_stats[4] = {0, 0, 0, 0}; // qe_ctx_last_window_stats: rows, partitions, scan tiles, trips of the tile-aggregate scan
     int64_t ordered_stats[4] = {0, 0, 0, 0}; // qe_ctx_last_ordered_stats: rows, groups, sorts run, radix passes of those sorts
+    int64_t set_stats[4] = {0, 0, 0, 0};    // qe_ctx_last_set_stats: left rows, right rows, distinct tuples the sort found, STRING columns translated
 };
 
 struct qe_host_result {

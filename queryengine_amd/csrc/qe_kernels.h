@@ -229,6 +229,27 @@ void launch_osa_count_distinct(hipStream_t s, const OsaGroups &g, const unsigned
 void launch_osa_mode(hipStream_t s, const OsaGroups &g, const uint32_t *runpos, const uint32_t *peer_prefix, const unsigned long long *pstart,
                      const uint32_t *pstart_prefix, unsigned long long *best);
 
+// ---- set operations over two concatenated, sorted results (qe_setop.hip) ----
+// grid cap, in blocks of 256 threads, of the two bitmap kernels (524 288 rows a sweep)
+constexpr int kSetopBlocks = 2048;
+// out[i] = table[codes[i]], i < n: the right side's STRING codes into the merged dictionary.  A code outside [0, ncodes) is
+// written as 0; nothing is skipped under a NULL
+void launch_setop_translate_codes(hipStream_t s, const int *codes, int64_t n, const int *table, int ncodes, int *out);
+// bit j of side = perm[j] < nleft: the row at sorted position j comes from the left input.  ceil(n / 64) whole words
+void launch_setop_side_bits(hipStream_t s, const uint32_t *perm, int64_t n, int64_t nleft, unsigned long long *side);
+// bit j of keep = (j - s) < k for the tuple [s, e) = [gstart[g], gstart[g + 1]) that holds j, g = rank of pstart at j; cL = side
+// bits in [s, e), cR = e - s - cL; k = QE_SET_UNION: all ? cL + cR : 1; INTERSECT: all ? min(cL, cR) : (cL && cR); EXCEPT: all ?
+// max(cL - cR, 0) : (cL && !cR).  *_prefix: the word ranks of bitmap_ranks (qe_scan.h).  ceil(n / 64) whole words
+struct SetopKeepArgs {
+    int op, all;                            // QE_SET_*, 0 / 1
+    long long n, ntuples;
+    const unsigned long long *pstart, *side;
+    const unsigned int *pstart_prefix, *side_prefix;
+    const unsigned int *gstart;             // ntuples + 1 entries, gstart[ntuples] = n
+    unsigned long long *keep;
+};
+void launch_setop_keep(hipStream_t s, const SetopKeepArgs &a);
+
 // ---- gathers through u32 row ids (qe_kernels.hip): ORDER BY, window, join, per-node ----
 // grid caps, in blocks of 256 threads: every caller's, and the join's output columns (with the narrow cap the probe was 0.4 to
 // 0.6 % slower than before in every interleaved run, with the wide one it is not: profiles/result_builder_refactor_summary.txt)

@@ -28,12 +28,6 @@ static unsigned osa_grid(i64 lanes, int max_blocks) {
     return (unsigned)(blocks < max_blocks ? blocks : max_blocks);
 }
 
-// set bits of `bits` below position i (0 <= i <= n; the bits past n are 0)
-__device__ __forceinline__ u32 osa_rank(const u64 *bits, const u32 *prefix, i64 i) {
-    const int b = (int)(i & 63);
-    return prefix[i >> 6] + (b ? (u32)__popcll(bits[i >> 6] & ((1ull << b) - 1ull)) : 0u);
-}
-
 // ---- first valid row per group ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) osa_first_valid_kernel(const OsaGroups a, const u64 *valid) {
     const i64 stride = (i64)gridDim.x * 256;
@@ -149,7 +143,7 @@ __global__ void __launch_bounds__(256) osa_count_distinct_kernel(const OsaGroups
         i64 first, c;
         osa_group_values(a, g, first, c);
         // the first valid row differs from the row before it (another group, or a NULL): it carries a peer bit
-        out[g] = (double)(osa_rank(peer, peer_prefix, first + c) - osa_rank(peer, peer_prefix, first));
+        out[g] = (double)(bitmap_rank(peer, peer_prefix, first + c) - bitmap_rank(peer, peer_prefix, first));
     }
 }
 void launch_osa_count_distinct(hipStream_t s, const OsaGroups &g, const unsigned long long *peer, const uint32_t *peer_prefix, double *out) {
@@ -170,7 +164,7 @@ __global__ void __launch_bounds__(256) osa_mode_kernel(const OsaGroups a, const 
         if (r < nruns) {
             const i64 p = runpos[r];
             if (p < a.n) {
-                const u32 gi = osa_rank(pstart, pstart_prefix, p + 1) - 1u;   // row 0 starts a group, so the rank is >= 1
+                const u32 gi = bitmap_rank(pstart, pstart_prefix, p + 1) - 1u;   // row 0 starts a group, so the rank is >= 1
                 if ((i64)gi < a.ngroups) {
                     g = gi;
                     i64 first, c;

@@ -57,6 +57,12 @@ __device__ __forceinline__ u64 keep_word(const u64 *v, const u64 *k, i64 w, i64 
     return x;
 }
 
+// set bits of `bits` below position i (0 <= i <= n; the bits past n are 0), from the word ranks that bitmap_ranks wrote
+__device__ __forceinline__ u32 bitmap_rank(const u64 *bits, const u32 *prefix, i64 i) {
+    const int b = (int)(i & 63);
+    return prefix[i >> 6] + (b ? (u32)__popcll(bits[i >> 6] & ((1ull << b) - 1ull)) : 0u);
+}
+
 // ---- what exclusive_scan sums: element i of an array, or the kept rows of bitmap word i ------------------------------------
 template <typename T> struct ArrayLoad {
     const T *p;

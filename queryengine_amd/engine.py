@@ -252,6 +252,22 @@ class Context:
         N.check(self.handle, self._lib.qe_ctx_last_ordered_stats(self.handle, out))
         return {"rows": int(out[0]), "groups": int(out[1]), "sorts": int(out[2]), "radix_passes": int(out[3])}
 
+    def set_op(self, left: "Result", right: "Result", op: int, all: bool = False) -> "Result":
+        """qe_result_set_op: UNION / INTERSECT / EXCEPT (native.SET_*) of two results of one schema, with `all` the multiset
+        form.  Rows are equal as group keys are (NULL equals NULL, every NaN one value, -0.0 is not 0.0, strings by string; the
+        sides may carry different dictionaries: the output then carries the merged one).  UNION ALL is left's rows, then
+        right's; every other form comes out ascending by all columns (NULL first)."""
+        h = C.c_void_p()
+        N.check(self.handle, self._lib.qe_result_set_op(self.handle, left.handle, right.handle, int(op), int(all), C.byref(h)))
+        return Result(self, h)
+
+    def last_set_stats(self) -> dict:
+        """qe_ctx_last_set_stats: left rows, right rows, distinct tuples the sort found (0 for UNION ALL) and STRING columns
+        whose right-side codes were translated, of the last set_op()."""
+        out = (C.c_int64 * 4)()
+        N.check(self.handle, self._lib.qe_ctx_last_set_stats(self.handle, out))
+        return {"left_rows": int(out[0]), "right_rows": int(out[1]), "tuples": int(out[2]), "translated_columns": int(out[3])}
+
     def concat(self, parts: Sequence["Result"]) -> "Result":
         """qe_result_concat: results of this device, concatenated in the given order."""
         arr = (C.c_void_p * max(1, len(parts)))(*[p.handle for p in parts])

@@ -38,6 +38,8 @@ OSA_COUNT_DISTINCT, OSA_PERCENTILE_CONT, OSA_PERCENTILE_DISC, OSA_MODE = range(4
 OSA_BLOCKS = 1024                            # its grid cap in blocks of 256 lanes: a lane per group or run
 OSA_WORD_BLOCKS = 128                        # 128 * 256 words = 2^21 rows: a size the ordered tests stay above (once a grid cap of its own
                                              # lane-per-word kernels; those are the shared ones of DESIGN.md 3.11 now)
+SET_UNION, SET_INTERSECT, SET_EXCEPT = range(3)   # qe_result_set_op
+SETOP_BLOCKS = 2048                          # grid cap of its two bitmap kernels in blocks of 256 lanes (kSetopBlocks)
 
 
 class QeError(RuntimeError):
@@ -173,6 +175,8 @@ SYMBOLS = [
     ("qe_ctx_last_window_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_result_group_ordered", C.c_int32, [_P, _P, C.POINTER(C.c_int32), C.c_int32, C.POINTER(OrderedAgg), C.c_int32, C.POINTER(_P)]),
     ("qe_ctx_last_ordered_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
+    ("qe_result_set_op", C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    ("qe_ctx_last_set_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_batch_from_result", C.c_int32, [_P, _P, C.POINTER(_P)]),
     ("qe_comm_unique_id", C.c_int32, [_P, _P]),
     ("qe_comm_init", C.c_int32, [_P, C.c_int32, C.c_int32, _P]),

@@ -592,6 +592,123 @@ class OrderedAggregateOperator(Operator):
             self._result = None
 
 
+class SetOperator(Operator):
+    """UNION / INTERSECT / EXCEPT of two sources of one schema (``op`` one of ``native.SET_UNION / SET_INTERSECT / SET_EXCEPT``),
+    with ``all=True`` the multiset form.  Two rows are equal when they compare equal on every column the way group keys do
+    (``None`` equals ``None``, all NaNs are one value, -0.0 and 0.0 are two, strings by string).  Of a tuple that occurs cL times
+    on the left and cR times on the right the operator keeps: UNION 1, UNION ALL cL + cR; INTERSECT 1 if both sides hold it,
+    INTERSECT ALL min(cL, cR); EXCEPT 1 if only the left holds it, EXCEPT ALL max(cL - cR, 0).
+
+    UNION ALL yields the left rows in their order, then the right rows in theirs.  Every other form yields its rows ASCENDING by
+    column 0, then column 1, .. under the comparator of ``OrderByOperator`` (``None`` first), and the k copies of a tuple are its
+    first k rows in the sequence "left rows in input order, then right rows in input order": a kept row is a left row whenever
+    the tuple occurs on the left.  ``left`` and ``right`` may be the same operator; it is then drained once.  The reference has
+    no set operations (Query.g4 reads one table).
+
+    When both sources are GPU operators of one context (``result()`` and ``ctx``) the rows never leave HBM (qe_result_set_op)
+    and the operator offers ``result()`` and ``ctx`` itself.  Any other pair is drained and evaluated on the host: one stable
+    sort per column with ``_compare_key``, then one loop over the tuples -- the executable statement of the semantics, written
+    for clarity, and the expectation of the device tests."""
+
+    def __init__(self, left: Operator, right: Operator, op: int, all: bool = False):   # noqa: A002 (the SQL word)
+        if left is None or right is None:
+            raise ValueError("SetOperator: two sources")
+        if isinstance(op, bool) or not isinstance(op, int) or not N.SET_UNION <= op <= N.SET_EXCEPT:
+            raise ValueError("SetOperator: unknown op")
+        if all not in (False, True, 0, 1):
+            raise ValueError("SetOperator: all is False or True")
+        self.left, self.right = left, right
+        self.op, self.all = int(op), bool(all)
+        gpu = [hasattr(s, "result") and hasattr(s, "ctx") for s in (left, right)]
+        self._on_device = gpu[0] and gpu[1] and left.ctx is right.ctx
+        if self._on_device:
+            self.ctx = left.ctx
+        self._result: Optional[E.Result] = None
+        self._iter = None
+
+    @staticmethod
+    def _kept(op: int, all: bool, cl: int, cr: int) -> int:   # noqa: A002
+        """Copies kept of a tuple that occurs cl times on the left and cr times on the right."""
+        if op == N.SET_UNION:
+            return cl + cr if all else 1
+        if op == N.SET_INTERSECT:
+            return min(cl, cr) if all else int(cl > 0 and cr > 0)
+        return max(cl - cr, 0) if all else int(cl > 0 and cr == 0)
+
+    def _rows_host(self) -> List[List[Any]]:
+        left_rows = mapTo(self.left, [], lambda row: list(row))
+        right_rows = left_rows if self.right is self.left else mapTo(self.right, [], lambda row: list(row))
+        widths = {len(row) for row in left_rows} | {len(row) for row in right_rows}
+        if len(widths) > 1:
+            raise ValueError("SetOperator: the sides differ in their column counts")
+        if widths == {0}:
+            raise ValueError("SetOperator: no column")
+        for c in range(next(iter(widths), 0)):
+            kinds = {type(row[c]) for row in left_rows + right_rows if row[c] is not None}
+            if len(kinds) > 1:
+                raise ValueError(f"SetOperator: column {c} differs in type between the rows")
+        if self.op == N.SET_UNION and self.all:
+            return left_rows + right_rows
+        # (row, is left) in the sequence "left rows, then right rows"; the sorts are stable, so a tuple's left rows stay first
+        data = [(row, True) for row in left_rows] + [(row, False) for row in right_rows]
+        for column in reversed(range(next(iter(widths), 0))):
+            data.sort(key=lambda item: _compare_key(item[0][column]))
+        out = []
+        begin = 0
+        while begin < len(data):
+            end = begin + 1
+            while end < len(data) and all(_compare_key(a) == _compare_key(b) for a, b in zip(data[end][0], data[begin][0])):
+                end += 1
+            cl = sum(1 for _, is_left in data[begin:end] if is_left)
+            k = self._kept(self.op, self.all, cl, end - begin - cl)
+            out.extend(row for row, _ in data[begin:begin + k])
+            begin = end
+        return out
+
+    def _open_device(self) -> None:
+        self.left.open()
+        try:
+            if self.right is self.left:
+                self._result = self.ctx.set_op(self.left.result(), self.left.result(), self.op, self.all)
+                return
+            self.right.open()
+            try:
+                self._result = self.ctx.set_op(self.left.result(), self.right.result(), self.op, self.all)
+            finally:
+                self.right.close()
+        finally:
+            self.left.close()
+
+    def _device_rows(self):
+        cols = self._result.to_columns()
+        for i in range(self._result.count):
+            yield [c.value(i) for c in cols]
+
+    def open(self) -> None:
+        if self._on_device:
+            self._open_device()
+            self._iter = self._device_rows()
+        else:
+            self._iter = iter(self._rows_host())
+
+    def result(self) -> E.Result:
+        """The kept rows in HBM (valid until close()); only when both sources are GPU operators."""
+        if self._result is None:
+            raise RuntimeError("Operator not initialized")
+        return self._result
+
+    def next(self) -> Optional[List[Any]]:
+        if self._iter is None:
+            raise RuntimeError("Operator not opened")
+        return next(self._iter, None)
+
+    def close(self) -> None:
+        self._iter = None
+        if self._result is not None:
+            self._result.free()
+            self._result = None
+
+
 class ColumnarScanOperator(Operator):
     """Scan leaf over a ColumnarTable (replaces MemorySourceOperator.kt:5-36).
 
