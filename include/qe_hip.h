@@ -629,6 +629,69 @@ int32_t qe_result_set_op(qe_ctx *ctx, const qe_result *left, const qe_result *ri
  * into a merged dictionary */
 int32_t qe_ctx_last_set_stats(const qe_ctx *ctx, int64_t out[4]);
 
+/* ---- ASOF join of two results -----------------------------------------------------------------------------------
+ * For every left row the ONE right row of the same by tuple whose `on` value is nearest at or before it (QE_ASOF_BACKWARD) or
+ * at or after it (QE_ASOF_FORWARD): for every trade the last quote of its symbol, for every event the next calibration reading
+ * of its sensor.  The hash join (qe_join_build / qe_join_probe) matches on equality only, a window cannot look into another
+ * result and the set operations need one schema on both sides.  The reference has no join at all (Query.g4 reads one table).
+ *
+ * Keys: 0 <= nby <= 7 (the by columns and the `on` column are the sort's 8 keys).  By column i of the left pairs with by
+ * column i of the right; the two have the same type, any of the five.  Two by tuples are equal as hash-join keys are
+ * (Double.equals: every NaN is one value, -0.0 is not 0.0; STRING compares by string, the sides may carry different
+ * dictionaries), and a NULL in any by column, on either side, matches nothing.  nby == 0: the whole input is one partition.
+ *
+ * The `on` column is DOUBLE, INT64 or INT32, the same type on both sides, and is compared in its own type under the comparator
+ * of qe_result_order_by_keys: Double.compareTo for DOUBLE (-0.0 < 0.0, NaN greatest, all NaNs equal), integer order for the
+ * integer types -- INT64 values beyond 2^53 never go through a double.  A NULL `on` matches nothing, on either side.
+ *
+ * The match of a left row l.  Candidates are the right rows r with an equal by tuple and a valid `on`.
+ *   QE_ASOF_BACKWARD: cmp(on(r), on(l)) <= 0 (< 0 when strict); of those the greatest on(r); of several with that value the one
+ *     with the greatest right row index.
+ *   QE_ASOF_FORWARD:  cmp(on(r), on(l)) >= 0 (> 0 when strict); of those the smallest on(r); of several with that value the one
+ *     with the smallest right row index.
+ * A left row matches exactly one right row, or none.
+ *
+ * Rows and order.  QE_JOIN_LEFT: one output row per left row, in left input order; where there is no match every right column
+ * is NULL (validity 0, value zero).  QE_JOIN_INNER: only the matched left rows, in left input order.
+ *
+ * Columns: the listed left columns, then the listed right columns.  A column may be listed twice and either list may be empty,
+ * but there is at least one output column.  A STRING column carries its source's dictionary (merged dictionaries are scratch
+ * for the keys only); nullability is the source's, and under QE_JOIN_LEFT every right column is nullable.  `left` and `right`
+ * may be the same handle.
+ *
+ * Determinism: the same inputs give the same bytes on every run and every context.  No atomic feeds a result byte (the one
+ * atomic is the integer count of partitions of the boundary flags).
+ *
+ * Limits and errors (*out = NULL): QE_ERR_INVALID_ARG for a null pointer (left_by / right_by may be null when nby == 0, a column
+ * list when its count is 0), nby outside 0..7, direction outside 0..1, strict other than 0 or 1, a join_type other than
+ * QE_JOIN_INNER or QE_JOIN_LEFT, a negative column count, no output column -- these are checked before either result is read --
+ * a column out of range, paired by columns of different types, an `on` column that is not DOUBLE, INT64 or INT32 or whose type
+ * differs between the sides, a STRING by column without a dictionary; QE_ERR_UNSUPPORTED for left rows + right rows > 2^32 - 2;
+ * QE_ERR_HIP on a planning-only context; QE_ERR_OOM when scratch or output does not fit.  Zero rows on either side is an
+ * ordinary input and returns the full schema.
+ *
+ * Lifetime and reuse: the output owns its buffers and shares the dictionaries; both inputs may be freed once the call returns.
+ * The output is an ordinary result (qe_batch_from_result, qe_result_order_by_keys, ..).
+ *
+ * How: the nby + 1 key columns of both sides are concatenated into a scratch result (right STRING codes through the set
+ * operations' translation table) -- the right rows first for (BACKWARD, not strict) and (FORWARD, strict), the left rows first
+ * for the other two, so that the stable sort over (by.., on) lets ties fall the way the match is defined; the boundary flags of
+ * the window operator mark the partition starts; one pass marks the sorted positions whose row is valid in every key, and
+ * those of them that hold a right row; a second pass, with fixed work per left row, takes the nearest marked right position
+ * before (after) its own from the ranks and positions of that bitmap and accepts it when no partition starts in between.  The
+ * row gather every operator uses builds the output. */
+enum { QE_ASOF_BACKWARD = 0, QE_ASOF_FORWARD = 1 };
+int32_t qe_result_asof_join(qe_ctx *ctx, const qe_result *left, const qe_result *right,
+                            const int32_t *left_by, const int32_t *right_by, int32_t nby,
+                            int32_t left_on, int32_t right_on,
+                            int32_t direction, int32_t strict, int32_t join_type,   /* QE_JOIN_INNER or QE_JOIN_LEFT */
+                            const int32_t *left_out, int32_t nleft_out,
+                            const int32_t *right_out, int32_t nright_out, qe_result **out);
+/* what the last qe_result_asof_join of this context did: out[0] left rows, out[1] right rows, out[2] left rows that found a
+ * match, out[3] by partitions the sort found over both sides together (NULL counts as a key value there; 0 when there are no
+ * rows at all) */
+int32_t qe_ctx_last_asof_stats(const qe_ctx *ctx, int64_t out[4]);
+
 /* zero-copy: a batch whose columns ARE the result's (not owned; the result must outlive the batch).  Same columns, same
  * validity (NULL where the result has none), same dictionaries, nrows = the result's count (zero rows: a zero-row batch).
  * The batch goes into qe_filter_project / qe_filter_aggregate / qe_filter_groupby like any other: that is how a join is

@@ -78,6 +78,12 @@ internal object QeNative {
     // dictionaries); UNION ALL is left's rows then right's, every other form ascending by all columns
     val qe_result_set_op = handle("qe_result_set_op", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, ADDRESS)
     val qe_ctx_last_set_stats = handle("qe_ctx_last_set_stats", JAVA_INT, ADDRESS, ADDRESS)           // ctx, long[4]
+    // ---- ASOF join of two results: direction 0 BACKWARD (nearest at or before), 1 FORWARD (at or after); strict 0 / 1; join_type 0 INNER, 1 LEFT ----
+    // ctx, left, right, int[] left_by, int[] right_by, nby (0..7), left_on, right_on, direction, strict, join_type, int[] left_out, nleft_out,
+    // int[] right_out, nright_out, qe_result** -> status: per left row the one right row of its by tuple with the nearest `on`, in left row order
+    val qe_result_asof_join = handle("qe_result_asof_join", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT,
+        JAVA_INT, JAVA_INT, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS)
+    val qe_ctx_last_asof_stats = handle("qe_ctx_last_asof_stats", JAVA_INT, ADDRESS, ADDRESS)         // ctx, long[4]
     // ctx, result, qe_batch** -> status: a batch whose columns ARE the result's (zero copy): the input of the next plan
     val qe_batch_from_result = handle("qe_batch_from_result", JAVA_INT, ADDRESS, ADDRESS, ADDRESS)
 

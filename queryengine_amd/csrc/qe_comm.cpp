@@ -159,6 +159,15 @@ ResultPtr concat_output(qe_ctx *ctx, const qe_result *like, int64_t total, uint3
     return out;
 }
 
+// `ncols` columns of `src` as a result of their own that only borrows the buffers: for a caller that concatenates a column
+// subset of a wider result.  It is never handed to free_result.
+qe_result column_view(const qe_result *src, const int32_t *cols, int32_t ncols) {
+    qe_result view;
+    view.count = view.capacity = src->count;
+    for (int32_t i = 0; i < ncols; i++) view.cols.push_back(src->cols[(size_t)cols[i]]);
+    return view;
+}
+
 static uint64_t *ones_bitmap(qe_ctx *ctx, PoolScratch &sc, int64_t n) {
     uint64_t *p = (uint64_t *)sc.alloc(bitmap_bytes(n));
     QE_HIP(hipMemsetAsync(p, 0xff, bitmap_bytes(n), ctx->stream));

@@ -15,6 +15,8 @@
 //                    window's boundary flags, then ranks, compaction and picks over the sorted rows
 //   qe_setop.cpp     UNION / INTERSECT / EXCEPT [ALL] of two results: the concatenation, one sort over every column, the
 //                    boundary flags, a keep bitmap from per-tuple counts of the two sides, the row gather
+//   qe_asof.cpp      the ASOF join of two results: the key columns concatenated, one sort over (by.., on), the boundary
+//                    flags, the nearest eligible right position per left row, the row gather
 #pragma once
 
 #include <memory>
@@ -125,12 +127,23 @@ struct SortDriver {
     void sort(RadixBuffers &rb, bool identity);
 };
 
-// ---- qe_comm.cpp: the placement code behind qe_result_concat / qe_gather, shared with the set operations -------------------
+// ---- qe_comm.cpp: the placement code behind qe_result_concat / qe_gather, shared with the set operations and the ASOF join --
 // A result of `total` rows with the column types and dictionaries of `like`; bit c of any_validity: column c carries a
 // validity bitmap.  BOOLEAN values and validity are zeroed: concat_place ORs segments in.
 ResultPtr concat_output(qe_ctx *ctx, const qe_result *like, int64_t total, uint32_t any_validity);
 // the rows of `part` at row offset `off` of such a result (bit c of skip_values: the caller writes column c's values itself)
 void concat_place(qe_ctx *ctx, PoolScratch &sc, const qe_result *part, int64_t off, qe_result *out, uint32_t skip_values);
+// `ncols` columns of `src` as a result that borrows their buffers (never freed): what the two take for a column subset
+qe_result column_view(const qe_result *src, const int32_t *cols, int32_t ncols);
+
+// ---- qe_setop.cpp: the merged dictionary of a STRING column whose sides carry different dictionary objects --------------------
+// dict: the left entries in their order, then the right entries the left does not hold, in the right's order; table[right
+// code] = merged code (an entry the left holds: the code the left finds for it).  Shared with the ASOF join's by columns.
+struct MergedDict {
+    std::shared_ptr<DictData> dict;
+    std::vector<int32_t> table;
+};
+MergedDict merge_dictionaries(const DictData &left, const DictData &right);
 
 // ---- qe_api.cpp: plans and launches -------------------------------------------------------------------------
 // What get_plan is asked for; a call site names only what it sets.

@@ -439,6 +439,7 @@ struct qe_ctx {
     int64_t window_stats[4] = {0, 0, 0, 0}; // qe_ctx_last_window_stats: rows, partitions, scan tiles, trips of the tile-aggregate scan
     int64_t ordered_stats[4] = {0, 0, 0, 0}; // qe_ctx_last_ordered_stats: rows, groups, sorts run, radix passes of those sorts
     int64_t set_stats[4] = {0, 0, 0, 0};    // qe_ctx_last_set_stats: left rows, right rows, distinct tuples the sort found, STRING columns translated
+    int64_t asof_stats[4] = {0, 0, 0, 0};   // qe_ctx_last_asof_stats: left rows, right rows, left rows that found a match, by partitions of the sort
 };
 
 struct qe_host_result {

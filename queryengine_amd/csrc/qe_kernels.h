@@ -250,6 +250,43 @@ struct SetopKeepArgs {
 };
 void launch_setop_keep(hipStream_t s, const SetopKeepArgs &a);
 
+// ---- ASOF join over two concatenated, sorted key sets (qe_asof.hip) ----
+// grid cap, in blocks of 256 threads, of its three kernels (524 288 rows a sweep)
+constexpr int kAsofBlocks = 2048;
+// Where the rows of the two sides stand: the concatenation holds `nfirst` rows of one side, then the other side's; right_first:
+// the first side is the right one.  perm[j] = row of the concatenation at sorted position j.
+struct AsofSides {
+    const unsigned int *perm;
+    long long n, nfirst;
+    int right_first;
+};
+// bit j of eligible = the row at sorted position j is valid in every key column (validity[k] null: no NULL in that column),
+// bit j of right = it is eligible and a right row.  ceil(n / 64) whole words each
+struct AsofEligibleArgs {
+    AsofSides s;
+    int nkeys;
+    const unsigned long long *validity[8];  // of the concatenated key columns
+    unsigned long long *eligible, *right;
+};
+void launch_asof_eligible(hipStream_t s, const AsofEligibleArgs &a);
+// match[l] = the right row of left row l, or 0xFFFFFFFF, written by the sorted position j that holds l -- every left row once.
+// An eligible left row takes k = set bits of `right` below j and the candidate position rpos[k - 1] (backward; none when
+// k == 0) or rpos[k] (forward; none when k == the set bits of `right`, which is right_prefix's last entry), and accepts it when pstart has no set bit in (candidate, j] (backward) or
+// (j, candidate] (forward): both stand in one partition.  *_prefix: the word ranks of bitmap_ranks (qe_scan.h)
+struct AsofPickArgs {
+    AsofSides s;
+    int forward;
+    long long nleft;                        // left rows = entries of match; rpos has room for the n - nleft right rows
+    const unsigned long long *eligible, *right, *pstart;
+    const unsigned int *right_prefix, *pstart_prefix;
+    const unsigned int *rpos;               // ascending positions of the set bits of `right`
+    unsigned int *match;
+};
+void launch_asof_pick(hipStream_t s, const AsofPickArgs &a);
+// bit l of matched = match[l] != 0xFFFFFFFF, l < nleft, whole words; identity[l] = l when identity is not null (the rows of
+// the LEFT form's own side)
+void launch_asof_matched(hipStream_t s, const uint32_t *match, int64_t nleft, unsigned long long *matched, uint32_t *identity);
+
 // ---- gathers through u32 row ids (qe_kernels.hip): ORDER BY, window, join, per-node ----
 // grid caps, in blocks of 256 threads: every caller's, and the join's output columns (with the narrow cap the probe was 0.4 to
 // 0.6 % slower than before in every interleaved run, with the wide one it is not: profiles/result_builder_refactor_summary.txt)

@@ -10,6 +10,27 @@
 #include "qe_scan.h"
 
 namespace qe {
+
+MergedDict merge_dictionaries(const DictData &left, const DictData &right) {
+    MergedDict md;
+    md.dict = std::make_shared<DictData>();
+    md.dict->entries = left.entries;
+    md.dict->index = left.index;
+    md.table.resize(right.entries.size());
+    for (size_t i = 0; i < md.table.size(); i++) {
+        const std::string &s = right.entries[i];
+        const int32_t found = left.find(s);
+        if (found >= 0) {
+            md.table[i] = found;
+            continue;
+        }
+        md.table[i] = (int32_t)md.dict->entries.size();
+        md.dict->index.emplace(s, md.table[i]);   // first occurrence wins
+        md.dict->entries.push_back(s);
+    }
+    return md;
+}
+
 namespace {
 
 constexpr int kMaxSortedCols = 8, kMaxConcatCols = 16;   // the sort's keys; the limit of qe_result_concat
@@ -50,21 +71,9 @@ qe_result *run_set_op(qe_ctx *ctx, const qe_result *left, const qe_result *right
         const OutColumn &l = left->cols[(size_t)c], &r = right->cols[(size_t)c];
         if (is_nullable(l) || is_nullable(r)) any_validity |= 1u << c;
         if (l.type != QE_STRING || l.dict.get() == r.dict.get()) continue;
-        auto m = std::make_shared<DictData>();
-        m->entries = l.dict->entries;
-        m->index = l.dict->index;
-        std::vector<int32_t> table(r.dict->entries.size());
-        for (size_t i = 0; i < table.size(); i++) {
-            const std::string &s = r.dict->entries[i];
-            const int32_t found = l.dict->find(s);
-            if (found >= 0) {
-                table[i] = found;
-                continue;
-            }
-            table[i] = (int32_t)m->entries.size();
-            m->index.emplace(s, table[i]);   // first occurrence wins
-            m->entries.push_back(s);
-        }
+        MergedDict md = merge_dictionaries(*l.dict, *r.dict);
+        std::shared_ptr<DictData> m = std::move(md.dict);
+        std::vector<int32_t> table = std::move(md.table);
         int *d = (int *)sc.alloc(table.size() * 4);
         tables.push_back(std::move(table));
         if (!tables.back().empty())

@@ -268,6 +268,27 @@ class Context:
         N.check(self.handle, self._lib.qe_ctx_last_set_stats(self.handle, out))
         return {"left_rows": int(out[0]), "right_rows": int(out[1]), "tuples": int(out[2]), "translated_columns": int(out[3])}
 
+    def asof_join(self, left: "Result", right: "Result", left_by: Sequence[int], right_by: Sequence[int], left_on: int, right_on: int,
+                  direction: int = N.ASOF_BACKWARD, strict: bool = False, join_type: int = N.JOIN_LEFT,
+                  left_out: Sequence[int] = (), right_out: Sequence[int] = ()) -> "Result":
+        """qe_result_asof_join: per left row the one right row with an equal by tuple (as hash-join keys are equal; a NULL
+        matches nothing) whose `on` value is nearest at or before it (native.ASOF_BACKWARD) or at or after it (ASOF_FORWARD),
+        `strict` excluding an equal `on`; ties go to the greatest (backward) / smallest (forward) right row.  The listed left
+        columns, then the listed right columns, in left row order: every left row (JOIN_LEFT, the right columns NULL without a
+        match) or the matched ones (JOIN_INNER)."""
+        h = C.c_void_p()
+        N.check(self.handle, self._lib.qe_result_asof_join(
+            self.handle, left.handle, right.handle, _i32_array(left_by), _i32_array(right_by), len(left_by), int(left_on), int(right_on),
+            int(direction), int(strict), int(join_type), _i32_array(left_out), len(left_out), _i32_array(right_out), len(right_out), C.byref(h)))
+        return Result(self, h)
+
+    def last_asof_stats(self) -> dict:
+        """qe_ctx_last_asof_stats: left rows, right rows, left rows that found a match and by partitions the sort found over
+        both sides together, of the last asof_join()."""
+        out = (C.c_int64 * 4)()
+        N.check(self.handle, self._lib.qe_ctx_last_asof_stats(self.handle, out))
+        return {"left_rows": int(out[0]), "right_rows": int(out[1]), "matched": int(out[2]), "partitions": int(out[3])}
+
     def concat(self, parts: Sequence["Result"]) -> "Result":
         """qe_result_concat: results of this device, concatenated in the given order."""
         arr = (C.c_void_p * max(1, len(parts)))(*[p.handle for p in parts])

@@ -40,6 +40,8 @@ OSA_WORD_BLOCKS = 128                        # 128 * 256 words = 2^21 rows: a si
                                              # lane-per-word kernels; those are the shared ones of DESIGN.md 3.11 now)
 SET_UNION, SET_INTERSECT, SET_EXCEPT = range(3)   # qe_result_set_op
 SETOP_BLOCKS = 2048                          # grid cap of its two bitmap kernels in blocks of 256 lanes (kSetopBlocks)
+ASOF_BACKWARD, ASOF_FORWARD = range(2)       # qe_result_asof_join
+ASOF_BLOCKS = 2048                           # grid cap of its three kernels in blocks of 256 lanes (kAsofBlocks)
 
 
 class QeError(RuntimeError):
@@ -177,6 +179,10 @@ SYMBOLS = [
     ("qe_ctx_last_ordered_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_result_set_op", C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(_P)]),
     ("qe_ctx_last_set_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
+    ("qe_result_asof_join", C.c_int32, [_P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                        C.POINTER(_P)]),
+    ("qe_ctx_last_asof_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_batch_from_result", C.c_int32, [_P, _P, C.POINTER(_P)]),
     ("qe_comm_unique_id", C.c_int32, [_P, _P]),
     ("qe_comm_init", C.c_int32, [_P, C.c_int32, C.c_int32, _P]),

@@ -709,6 +709,150 @@ class SetOperator(Operator):
             self._result = None
 
 
+class AsofJoinOperator(Operator):
+    """ASOF join: for every left row the ONE right row with an equal by tuple whose ``on`` value is nearest at or before it
+    (``direction=native.ASOF_BACKWARD``) or at or after it (``ASOF_FORWARD``) -- for every trade the last quote of its symbol.
+    ``left_by[i]`` pairs with ``right_by[i]`` (column indices, 0 to 7 of them; none: the whole input is one partition); by
+    tuples are equal as hash-join keys are (every NaN one value, -0.0 and 0.0 two, strings by string) and a ``None`` in a by
+    column or in ``on``, on either side, matches nothing.  ``on`` is numeric and compares like ``OrderByOperator`` compares
+    (``Double.compareTo``; integers exactly).
+
+    BACKWARD takes, of the right rows with ``on(r) <= on(l)`` (``<`` when ``strict``), the greatest ``on(r)`` and of several
+    with that value the LAST right row; FORWARD, of those with ``on(r) >= on(l)`` (``>``), the smallest and of several the
+    FIRST.  A row is the listed left columns followed by the listed right columns (``None`` = every column of that side), in
+    left row order: every left row under ``native.JOIN_LEFT`` (the right columns ``None`` without a match), the matched ones
+    under ``JOIN_INNER``.  ``left`` and ``right`` may be the same operator; it is then drained once.  The reference has no
+    join (Query.g4 reads one table).
+
+    When both sources are GPU operators of one context (``result()`` and ``ctx``) the rows never leave HBM
+    (qe_result_asof_join) and the operator offers ``result()`` and ``ctx`` itself.  Any other pair is drained and joined on the
+    host by a plain nested loop over ``_join_key`` and ``_compare_key`` -- the executable statement of the semantics, written
+    for clarity, and the expectation of the device tests."""
+
+    def __init__(self, left: Operator, right: Operator, left_by: Sequence[int], right_by: Sequence[int], left_on: int, right_on: int,
+                 direction: int = N.ASOF_BACKWARD, strict: bool = False, join_type: int = N.JOIN_LEFT,
+                 left_out: Optional[Sequence[int]] = None, right_out: Optional[Sequence[int]] = None):
+        if left is None or right is None:
+            raise ValueError("AsofJoinOperator: two sources")
+        self.left, self.right = left, right
+        self.left_by, self.right_by = [int(c) for c in left_by], [int(c) for c in right_by]
+        if len(self.left_by) > 7 or len(self.left_by) != len(self.right_by):
+            raise ValueError("AsofJoinOperator: 0 to 7 by columns, as many on the left as on the right")
+        self.left_on, self.right_on = int(left_on), int(right_on)
+        if isinstance(direction, bool) or direction not in (N.ASOF_BACKWARD, N.ASOF_FORWARD):
+            raise ValueError("AsofJoinOperator: unknown direction")
+        if strict not in (False, True, 0, 1):
+            raise ValueError("AsofJoinOperator: strict is False or True")
+        if isinstance(join_type, bool) or join_type not in (N.JOIN_INNER, N.JOIN_LEFT):
+            raise ValueError("AsofJoinOperator: the join type is INNER or LEFT")
+        self.direction, self.strict, self.join_type = int(direction), bool(strict), int(join_type)
+        self.left_out = None if left_out is None else [int(c) for c in left_out]
+        self.right_out = None if right_out is None else [int(c) for c in right_out]
+        if self.left_out is not None and self.right_out is not None and not self.left_out + self.right_out:
+            raise ValueError("AsofJoinOperator: no output column")
+        gpu = [hasattr(s, "result") and hasattr(s, "ctx") for s in (left, right)]
+        self._on_device = gpu[0] and gpu[1] and left.ctx is right.ctx
+        if self._on_device:
+            self.ctx = left.ctx
+        self._result: Optional[E.Result] = None
+        self._iter = None
+
+    @staticmethod
+    def _on_key(value: Any):
+        if value is not None and (isinstance(value, bool) or not isinstance(value, (int, float))):
+            raise ValueError("AsofJoinOperator: the on column is numeric")
+        return None if value is None else _compare_key(value)
+
+    def _match(self, row: List[Any], right_rows: List[List[Any]]) -> Optional[List[Any]]:
+        """The right row that `row` matches, or None."""
+        key, on = _join_key([row[c] for c in self.left_by]), self._on_key(row[self.left_on])
+        if key is None or on is None:
+            return None
+        best, best_on = None, None
+        for r in right_rows:                                   # in right row order
+            r_on = self._on_key(r[self.right_on])
+            if r_on is None or _join_key([r[c] for c in self.right_by]) != key:
+                continue
+            if isinstance(r[self.right_on], float) != isinstance(row[self.left_on], float):
+                raise ValueError("AsofJoinOperator: the on column differs in type between the sides")
+            if self.direction == N.ASOF_BACKWARD:
+                if (r_on < on or (r_on == on and not self.strict)) and (best is None or r_on >= best_on):   # >=: the last of equals
+                    best, best_on = r, r_on
+            elif (r_on > on or (r_on == on and not self.strict)) and (best is None or r_on < best_on):      # <: the first of equals
+                best, best_on = r, r_on
+        return best
+
+    def _rows_host(self) -> List[List[Any]]:
+        left_rows = mapTo(self.left, [], lambda row: list(row))
+        right_rows = left_rows if self.right is self.left else mapTo(self.right, [], lambda row: list(row))
+        right_out = self.right_out
+        if right_out is None:
+            if right_rows:
+                right_out = list(range(len(right_rows[0])))
+            elif self.join_type == N.JOIN_LEFT and left_rows:
+                raise ValueError("AsofJoinOperator: right_out must be given when a LEFT join's right source yields no row")
+            else:
+                right_out = []
+        out = []
+        for row in left_rows:
+            head = [row[c] for c in (range(len(row)) if self.left_out is None else self.left_out)]
+            match = self._match(row, right_rows)
+            if match is not None:
+                out.append(head + [match[c] for c in right_out])
+            elif self.join_type == N.JOIN_LEFT:
+                out.append(head + [None] * len(right_out))
+        return out
+
+    def _join_device(self, lres: E.Result, rres: E.Result) -> E.Result:
+        left_out = list(range(lres.ncols)) if self.left_out is None else self.left_out
+        right_out = list(range(rres.ncols)) if self.right_out is None else self.right_out
+        return self.ctx.asof_join(lres, rres, self.left_by, self.right_by, self.left_on, self.right_on, self.direction, self.strict,
+                                  self.join_type, left_out, right_out)
+
+    def _open_device(self) -> None:
+        self.left.open()
+        try:
+            if self.right is self.left:
+                self._result = self._join_device(self.left.result(), self.left.result())
+                return
+            self.right.open()
+            try:
+                self._result = self._join_device(self.left.result(), self.right.result())
+            finally:
+                self.right.close()
+        finally:
+            self.left.close()
+
+    def _device_rows(self):
+        cols = self._result.to_columns()
+        for i in range(self._result.count):
+            yield [c.value(i) for c in cols]
+
+    def open(self) -> None:
+        if self._on_device:
+            self._open_device()
+            self._iter = self._device_rows()
+        else:
+            self._iter = iter(self._rows_host())
+
+    def result(self) -> E.Result:
+        """The joined columns in HBM (valid until close()); only when both sources are GPU operators."""
+        if self._result is None:
+            raise RuntimeError("Operator not initialized")
+        return self._result
+
+    def next(self) -> Optional[List[Any]]:
+        if self._iter is None:
+            raise RuntimeError("Operator not opened")
+        return next(self._iter, None)
+
+    def close(self) -> None:
+        self._iter = None
+        if self._result is not None:
+            self._result.free()
+            self._result = None
+
+
 class ColumnarScanOperator(Operator):
     """Scan leaf over a ColumnarTable (replaces MemorySourceOperator.kt:5-36).
 
