@@ -1,7 +1,7 @@
 // qe_asof.cpp -- host side of the ASOF join of two results (kernels: qe_asof.hip): for every left row the one
 // right row of the same by tuple whose `on` value is nearest at or before (after) it.  The key columns of the two sides are
-// concatenated with the placement code of qe_result_concat, sorted once by (by.., on) with the ORDER BY driver and marked with
-// the window operator's boundary flags; two kernels find, per left row, the nearest eligible right position inside its
+// concatenated with their STRING dictionaries settled (concat_two_sided, qe_exec.h), sorted once by (by.., on) and marked
+// with the partition starts (SortedRuns, qe_exec.h); two kernels find, per left row, the nearest eligible right position inside its
 // partition, and the row gather every operator uses builds the output.
 #include <algorithm>
 
@@ -12,10 +12,7 @@
 namespace qe {
 namespace {
 
-constexpr int kMaxBy = 7;                        // with the `on` column: the sort's 8 keys
-constexpr int64_t kMaxRows = (1ll << 32) - 2;    // rows are uint32 with one sentinel, as in the join
-
-bool is_nullable(const OutColumn &c) { return c.nullable || c.validity != nullptr; }
+constexpr int kMaxBy = 7;   // with the `on` column: the sort's 8 keys
 
 struct AsofCall {
     const qe_result *left, *right;
@@ -79,52 +76,22 @@ qe_result *run_asof(qe_ctx *ctx, const AsofCall &q) {
     unsigned long long *matched = nullptr;
     uint32_t *matched_prefix = nullptr, *identity = nullptr;
     int64_t nmatched = 0;
-    ResultPtr cat(nullptr, ResultDeleter{ctx});   // the scratch key result: released with the scratch, after the last kernel
+    TwoSided both{own_result(ctx, nullptr)};   // the scratch key result: released with the scratch, after the last kernel
     if (n > 0) {
-        // ---- 1. the dictionaries of the STRING by columns, as the set operations settle them ----
+        // ---- 1. the scratch key result, the dictionaries of its STRING by columns settled.  The stable sort keeps the
+        // concatenation's order inside a run of equal keys: the right rows go first where a left row may match an equal `on`
+        // looking back, or may not match it looking forward ----
         const qe_result lview = column_view(left, lkeys.data(), nkeys), rview = column_view(right, rkeys.data(), nkeys);
-        std::vector<std::shared_ptr<DictData>> merged((size_t)nkeys);
-        std::vector<std::vector<int32_t>> tables;   // the host copies, alive until the uploads have completed
-        std::vector<const int *> d_table((size_t)nkeys, nullptr);
-        uint32_t translated_mask = 0, any_validity = 0;
-        tables.reserve((size_t)nkeys);
-        for (int32_t k = 0; k < nkeys; k++) {
-            const OutColumn &l = lview.cols[(size_t)k], &r = rview.cols[(size_t)k];
-            if (is_nullable(l) || is_nullable(r)) any_validity |= 1u << k;
-            if (l.type != QE_STRING || l.dict.get() == r.dict.get()) continue;
-            MergedDict md = merge_dictionaries(*l.dict, *r.dict);
-            int *d = (int *)sc.alloc(md.table.size() * 4);
-            tables.push_back(std::move(md.table));
-            if (!tables.back().empty())
-                QE_HIP(hipMemcpyAsync(d, tables.back().data(), tables.back().size() * 4, hipMemcpyHostToDevice, ctx->stream));
-            d_table[(size_t)k] = d;
-            merged[(size_t)k] = std::move(md.dict);
-            translated_mask |= 1u << k;
-        }
-
-        // ---- 2. the scratch key result.  The stable sort keeps the concatenation's order inside a run of equal keys: the right
-        // rows go first where a left row may match an equal `on` looking back, or may not match it looking forward ----
         const bool right_first = forward == (q.strict != 0);
-        const int64_t nfirst = right_first ? nr : nl, loff = right_first ? nr : 0, roff = right_first ? 0 : nl;
-        cat = concat_output(ctx, &lview, n, any_validity);
-        for (int32_t k = 0; k < nkeys; k++)
-            if (merged[(size_t)k]) cat->cols[(size_t)k].dict = cat->cols[(size_t)k].dict_handle.d = merged[(size_t)k];
-        concat_place(ctx, sc, &lview, loff, cat.get(), 0);
-        concat_place(ctx, sc, &rview, roff, cat.get(), translated_mask);
-        for (int32_t k = 0; k < nkeys; k++)
-            if (d_table[(size_t)k])
-                launch_setop_translate_codes(ctx->stream, (const int *)rview.cols[(size_t)k].data, nr, d_table[(size_t)k],
-                                             (int)rview.cols[(size_t)k].dict->entries.size(), (int *)cat->cols[(size_t)k].data + roff);
-        QE_HIP(hipGetLastError());
+        const int64_t nfirst = right_first ? nr : nl;
+        both = concat_two_sided(ctx, sc, &lview, right_first ? nr : 0, &rview, right_first ? 0 : nl);
+        const qe_result *cat = both.cat.get();
 
-        // ---- 3. one stable sort over (by.., on), and the partition starts through the same row ids ----
+        // ---- 2. one stable sort over (by.., on), and the partition starts through the same row ids ----
         std::vector<qe_sort_key> keys;
         for (int32_t k = 0; k < nkeys; k++) keys.push_back({k, 0});
-        SortDriver drv{ctx, sc, cat.get(), keys.data(), nkeys};
-        drv.prepare();
-        RadixBuffers rb(sc, n);
-        drv.sort(rb, true);
-        const uint32_t *perm = rb.sorted_rows();
+        SortedRuns runs(ctx, sc, cat, keys.data(), nkeys);
+        const uint32_t *perm = runs.rows;
         const int64_t nwords = bitmap_words(n);
         unsigned long long *pstart = (unsigned long long *)sc.alloc(bitmap_bytes(n));
         unsigned long long *peer = (unsigned long long *)sc.alloc(bitmap_bytes(n));   // the runs of equal `on`: not read
@@ -134,27 +101,10 @@ qe_result *run_asof(qe_ctx *ctx, const AsofCall &q) {
         uint32_t *sums = (uint32_t *)sc.alloc((size_t)scan_blocks(nwords + 1) * 4);
         uint32_t *pstart_prefix = (uint32_t *)sc.alloc((size_t)(nwords + 1) * 4);
         uint32_t *right_prefix = (uint32_t *)sc.alloc((size_t)(nwords + 1) * 4);
-        WinFlagArgs fa{};
-        fa.nkeys = nkeys;
-        fa.npart = q.nby;
-        fa.n = n;
-        fa.pstart = pstart;
-        fa.peer = peer;
-        fa.npartitions = d_count;
-        fa.perm = perm;
-        for (int32_t k = 0; k < nkeys; k++) {
-            const OutColumn &kc = cat->cols[(size_t)k];
-            fa.type[k] = kc.type;
-            fa.data[k] = kc.data;
-            fa.validity[k] = (const unsigned long long *)kc.validity;
-            fa.ranks[k] = drv.d_ranks[(size_t)k];
-            fa.nranks[k] = drv.nranks[(size_t)k];
-        }
-        QE_HIP(hipMemsetAsync(d_count, 0, 16, ctx->stream));
-        launch_win_flags(ctx->stream, fa);
-        bitmap_ranks(ctx->stream, (const uint64_t *)pstart, nullptr, n, pstart_prefix, sums, nullptr);
+        runs.flag(q.nby, pstart, peer, d_count);
+        runs.rank_starts(pstart, pstart_prefix, sums);
 
-        // ---- 4. the rows with a whole key, and the right rows among them ----
+        // ---- 3. the rows with a whole key, and the right rows among them ----
         AsofEligibleArgs ea{};
         ea.s = AsofSides{perm, n, nfirst, right_first ? 1 : 0};
         ea.nkeys = nkeys;
@@ -164,7 +114,7 @@ qe_result *run_asof(qe_ctx *ctx, const AsofCall &q) {
         launch_asof_eligible(ctx->stream, ea);
         bitmap_ranks(ctx->stream, (const uint64_t *)rbits, nullptr, n, right_prefix, sums, nullptr);
 
-        // ---- 5. the pick, and the matches as a bitmap over the left rows ----
+        // ---- 4. the pick, and the matches as a bitmap over the left rows ----
         if (nl > 0) {
             uint32_t *rpos = (uint32_t *)sc.alloc((size_t)(nr + 1) * 4);   // the eligible right rows are at most nr; the kernel reads their number
             match = (uint32_t *)sc.alloc((size_t)nl * 4);
@@ -191,15 +141,14 @@ qe_result *run_asof(qe_ctx *ctx, const AsofCall &q) {
         QE_HIP(hipMemcpyAsync(h_count, d_count, 16, hipMemcpyDeviceToHost, ctx->stream));   // the one read-back besides the sort's own
         QE_HIP(hipGetLastError());
         QE_HIP(hipStreamSynchronize(ctx->stream));
-        const int64_t G = (int64_t)h_count[0];
+        const int64_t G = checked_runs(who, h_count[0], "partitions", n);
         nmatched = (int64_t)h_count[1];
-        if (G < 1 || G > n) fail(QE_ERR_INTERNAL, std::string(who) + ": " + std::to_string(G) + " partitions of " + std::to_string(n) + " rows");
         if (nmatched < 0 || nmatched > nl) fail(QE_ERR_INTERNAL, std::string(who) + ": matched " + std::to_string(nmatched) + " of " + std::to_string(nl) + " left rows");
         stats[3] = G;
         stats[2] = nmatched;
     }
 
-    // ---- 6. the output: the listed left columns by the kept left rows, the listed right columns by their matches ----
+    // ---- 5. the output: the listed left columns by the kept left rows, the listed right columns by their matches ----
     const int64_t nout = inner ? nmatched : nl;
     ResultPtr res = new_result(ctx, nout);
     res->cols.reserve((size_t)(q.nleft_out + q.nright_out));
@@ -219,7 +168,7 @@ qe_result *run_asof(qe_ctx *ctx, const AsofCall &q) {
     for (int32_t i = 0; i < q.nright_out; i++) emit(right->cols[(size_t)q.right_out[i]], rrows, !inner);
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));   // the key result and the scratch go back to the pool now
-    for (int i = 0; i < 4; i++) ctx->asof_stats[i] = stats[i];
+    ctx->asof_stats.store(stats);
     return res.release();
 }
 
@@ -239,10 +188,6 @@ int32_t qe_result_asof_join(qe_ctx *ctx, const qe_result *left, const qe_result 
     return guarded(ctx, [&] { *out = run_asof(ctx, q); });
 }
 
-int32_t qe_ctx_last_asof_stats(const qe_ctx *ctx, int64_t out[4]) {
-    if (!ctx || !out) return QE_ERR_INVALID_ARG;
-    for (int i = 0; i < 4; i++) out[i] = ctx->asof_stats[i];
-    return QE_OK;
-}
+int32_t qe_ctx_last_asof_stats(const qe_ctx *ctx, int64_t out[4]) { return last_stats(ctx, &qe_ctx::asof_stats, out); }
 
 }  // extern "C"

@@ -194,6 +194,60 @@ void concat_place(qe_ctx *ctx, PoolScratch &sc, const qe_result *part, int64_t o
     }
 }
 
+MergedDict merge_dictionaries(const DictData &left, const DictData &right) {
+    MergedDict md;
+    md.dict = std::make_shared<DictData>();
+    md.dict->entries = left.entries;
+    md.dict->index = left.index;
+    md.table.resize(right.entries.size());
+    for (size_t i = 0; i < md.table.size(); i++) {
+        const std::string &s = right.entries[i];
+        const int32_t found = left.find(s);
+        if (found >= 0) {
+            md.table[i] = found;
+            continue;
+        }
+        md.table[i] = (int32_t)md.dict->entries.size();
+        md.dict->index.emplace(s, md.table[i]);   // first occurrence wins
+        md.dict->entries.push_back(s);
+    }
+    return md;
+}
+
+TwoSided concat_two_sided(qe_ctx *ctx, PoolScratch &sc, const qe_result *left, int64_t loff, const qe_result *right, int64_t roff) {
+    // the dictionaries: compare by string, not by code.  One object on both sides: the codes as they are
+    const size_t ncols = left->cols.size();
+    TwoSided out{own_result(ctx, nullptr)};
+    std::vector<std::shared_ptr<DictData>> merged(ncols);
+    std::vector<const int *> d_table(ncols, nullptr);
+    uint32_t any_validity = 0;
+    out.tables.reserve(ncols);
+    for (size_t c = 0; c < ncols; c++) {
+        const OutColumn &l = left->cols[c], &r = right->cols[c];
+        if (is_nullable(l) || is_nullable(r)) any_validity |= 1u << c;
+        if (l.type != QE_STRING || l.dict.get() == r.dict.get()) continue;
+        MergedDict md = merge_dictionaries(*l.dict, *r.dict);
+        int *d = (int *)sc.alloc(md.table.size() * 4);
+        out.tables.push_back(std::move(md.table));
+        if (!out.tables.back().empty())
+            QE_HIP(hipMemcpyAsync(d, out.tables.back().data(), out.tables.back().size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        d_table[c] = d;
+        merged[c] = std::move(md.dict);
+        out.translated |= 1u << c;
+    }
+    out.cat = concat_output(ctx, left, left->count + right->count, any_validity);
+    for (size_t c = 0; c < ncols; c++)
+        if (merged[c]) out.cat->cols[c].dict = out.cat->cols[c].dict_handle.d = merged[c];
+    concat_place(ctx, sc, left, loff, out.cat.get(), 0);
+    concat_place(ctx, sc, right, roff, out.cat.get(), out.translated);
+    for (size_t c = 0; c < ncols; c++)
+        if (d_table[c])
+            launch_setop_translate_codes(ctx->stream, (const int *)right->cols[c].data, right->count, d_table[c],
+                                         (int)right->cols[c].dict->entries.size(), (int *)out.cat->cols[c].data + roff);
+    QE_HIP(hipGetLastError());
+    return out;
+}
+
 }  // namespace qe
 
 using namespace qe;

@@ -6,17 +6,19 @@
 //                    exported, like qe_expr_rules.h, so that a test program can link it)
 //   qe_result.cpp    results on the device: how every operator builds one (new_result, add_column, gather_columns), and
 //                    their way to the host
-//   qe_sort.cpp      ORDER BY with top-k, and the stable multi-key radix sort (RadixBuffers, SortDriver) that the join build,
-//                    the window operator and the device group finish share with it
-//   qe_comm.cpp      the RCCL exchange step and the concatenation of results
+//   qe_sort.cpp      ORDER BY with top-k, the stable multi-key radix sort (RadixBuffers, SortDriver) that the join build and
+//                    the device group finish share with it, and that sort with the boundary flags of its runs (SortedRuns):
+//                    how the four sorted-run operators below begin
+//   qe_comm.cpp      the RCCL exchange step, the concatenation of results, and the two-sided concatenation with merged
+//                    dictionaries (concat_two_sided) that the set operations and the ASOF join begin with
 //   qe_join.cpp      the hash equi-join of two device-resident sides, a result as the next plan's batch
-//   qe_window.cpp    window functions over a result: the sort, the boundary flags, the segmented scans
-//   qe_ordered.cpp   ordered-set aggregates per group (quantiles, COUNT DISTINCT, MODE): one sort per argument column, the
-//                    window's boundary flags, then ranks, compaction and picks over the sorted rows
-//   qe_setop.cpp     UNION / INTERSECT / EXCEPT [ALL] of two results: the concatenation, one sort over every column, the
-//                    boundary flags, a keep bitmap from per-tuple counts of the two sides, the row gather
-//   qe_asof.cpp      the ASOF join of two results: the key columns concatenated, one sort over (by.., on), the boundary
-//                    flags, the nearest eligible right position per left row, the row gather
+//   qe_window.cpp    window functions over a result: sorted runs, the row gather, the segmented scans
+//   qe_ordered.cpp   ordered-set aggregates per group (quantiles, COUNT DISTINCT, MODE): sorted runs per argument column,
+//                    then ranks, compaction and picks over the sorted rows
+//   qe_setop.cpp     UNION / INTERSECT / EXCEPT [ALL] of two results: the two sides as one, sorted runs over every column,
+//                    a keep bitmap from per-tuple counts of the two sides, the row gather
+//   qe_asof.cpp      the ASOF join of two results: the key columns of the two sides as one, sorted runs over (by.., on),
+//                    the nearest eligible right position per left row, the row gather
 #pragma once
 
 #include <memory>
@@ -127,6 +129,25 @@ struct SortDriver {
     void sort(RadixBuffers &rb, bool identity);
 };
 
+// How the window, the ordered-set aggregates, the set operations and the ASOF join begin: the stable sort of src's rows by
+// `keys` from the identity, then the boundary flags of the sorted rows (qe_window.hip).  Everything is queued on the context's
+// stream and nothing is read back beyond what the sort reads itself (prepare, varying); the caller reads the counter when it
+// suits it.  The sort allocates from `ss` alone; the flag buffers are the caller's, so they may outlive `ss`.  The object
+// keeps the host rank tables of STRING keys, as SortDriver does: it lives as long as `ss`.
+struct SortedRuns {
+    SortDriver sorter;
+    const uint32_t *rows = nullptr;   // the sorted row ids, in `ss`; null without keys: no sort runs, the rows stay as they are
+    SortedRuns(qe_ctx *ctx, PoolScratch &ss, const qe_result *src, const qe_sort_key *keys, int32_t nkeys);
+    int64_t radix_passes() const { return sorter.radix_passes; }
+    // Zeroes the 16-byte counter, then launch_win_flags (qe_kernels.h) through `rows`: pstart = the starts of the runs of the
+    // first npart keys, peer = of all keys, word 0 of the counter = the set bits of pstart.  Bitmaps of bitmap_bytes(src->count).
+    void flag(int32_t npart, unsigned long long *pstart, unsigned long long *peer, unsigned long long *counter);
+    // prefix[w] = set bits of pstart before word w (bitmap_ranks; sums: its scan_blocks(words + 1) scratch)
+    void rank_starts(const unsigned long long *pstart, uint32_t *prefix, uint32_t *sums);
+};
+// the run count read back: who + ": <count> <noun> of <n> rows" (QE_ERR_INTERNAL) unless 1 <= count <= n
+int64_t checked_runs(const char *who, unsigned long long count, const char *noun, int64_t n);
+
 // ---- qe_comm.cpp: the placement code behind qe_result_concat / qe_gather, shared with the set operations and the ASOF join --
 // A result of `total` rows with the column types and dictionaries of `like`; bit c of any_validity: column c carries a
 // validity bitmap.  BOOLEAN values and validity are zeroed: concat_place ORs segments in.
@@ -136,14 +157,27 @@ void concat_place(qe_ctx *ctx, PoolScratch &sc, const qe_result *part, int64_t o
 // `ncols` columns of `src` as a result that borrows their buffers (never freed): what the two take for a column subset
 qe_result column_view(const qe_result *src, const int32_t *cols, int32_t ncols);
 
-// ---- qe_setop.cpp: the merged dictionary of a STRING column whose sides carry different dictionary objects --------------------
-// dict: the left entries in their order, then the right entries the left does not hold, in the right's order; table[right
-// code] = merged code (an entry the left holds: the code the left finds for it).  Shared with the ASOF join's by columns.
+constexpr int64_t kMaxRows = (1ll << 32) - 2;   // of a two-sided operator's sides together: rows are uint32 with one sentinel, as in the join
+inline bool is_nullable(const OutColumn &c) { return c.nullable || c.validity != nullptr; }
+// The merged dictionary of a STRING column whose sides carry different dictionary objects.  dict: the left entries in their
+// order, then the right entries the left does not hold, in the right's order; table[right code] = merged code (an entry the
+// left holds: the code the left finds for it).
 struct MergedDict {
     std::shared_ptr<DictData> dict;
     std::vector<int32_t> table;
 };
 MergedDict merge_dictionaries(const DictData &left, const DictData &right);
+// The two sides of a set operation or an ASOF join as one result of left->count + right->count rows, the left rows from
+// row loff on and the right rows from roff on.  The sides agree in their column types (the caller has checked, and that
+// every STRING column has a dictionary); a column is nullable when either side is; a STRING column whose sides differ in
+// dictionary object gets the merged dictionary and the right side's codes translated into it.  Queued on the context's
+// stream: the caller synchronises before it lets go of what this returns.
+struct TwoSided {
+    ResultPtr cat;
+    uint32_t translated = 0;                    // bit c: column c was translated
+    std::vector<std::vector<int32_t>> tables;   // the host copies of the translation tables, alive until the uploads have completed
+};
+TwoSided concat_two_sided(qe_ctx *ctx, PoolScratch &sc, const qe_result *left, int64_t loff, const qe_result *right, int64_t roff);
 
 // ---- qe_api.cpp: plans and launches -------------------------------------------------------------------------
 // What get_plan is asked for; a call site names only what it sets.

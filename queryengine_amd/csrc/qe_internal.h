@@ -395,6 +395,13 @@ struct FusedParams {
     unsigned long long *stats;
 };
 
+// What an operator's last call did, as its qe_ctx_last_*_stats call reports it.
+struct Stats4 {
+    int64_t w[4] = {0, 0, 0, 0};
+    void store(int64_t a, int64_t b, int64_t c, int64_t d) { w[0] = a, w[1] = b, w[2] = c, w[3] = d; }
+    void store(const int64_t (&s)[4]) { store(s[0], s[1], s[2], s[3]); }
+};
+
 }  // namespace qe
 
 struct qe_ctx {
@@ -434,12 +441,13 @@ struct qe_ctx {
     qe::PinnedPool pinned;
     std::vector<struct qe_host_result *> host_results;   // alive host results (their copies may still read a qe_result)
     qe_csv_device_stats csv_stats{};   // what the last qe_csv_parse*_device call did
-    int64_t sort_stats[4] = {0, 0, 0, 0};   // qe_ctx_last_sort_stats: path, rows sorted, radix passes, selection passes
-    int64_t join_stats[4] = {0, 0, 0, 0};   // qe_ctx_last_join_stats: build rows in the table, probe rows, output rows, longest run walked
-    int64_t window_stats[4] = {0, 0, 0, 0}; // qe_ctx_last_window_stats: rows, partitions, scan tiles, trips of the tile-aggregate scan
-    int64_t ordered_stats[4] = {0, 0, 0, 0}; // qe_ctx_last_ordered_stats: rows, groups, sorts run, radix passes of those sorts
-    int64_t set_stats[4] = {0, 0, 0, 0};    // qe_ctx_last_set_stats: left rows, right rows, distinct tuples the sort found, STRING columns translated
-    int64_t asof_stats[4] = {0, 0, 0, 0};   // qe_ctx_last_asof_stats: left rows, right rows, left rows that found a match, by partitions of the sort
+    // the four words a qe_ctx_last_*_stats call returns
+    qe::Stats4 sort_stats;     // path, rows sorted, radix passes, selection passes
+    qe::Stats4 join_stats;     // build rows in the table, probe rows, output rows, longest run walked
+    qe::Stats4 window_stats;   // rows, partitions, scan tiles, trips of the tile-aggregate scan
+    qe::Stats4 ordered_stats;  // rows, groups, sorts run, radix passes of those sorts
+    qe::Stats4 set_stats;      // left rows, right rows, distinct tuples the sort found, STRING columns translated
+    qe::Stats4 asof_stats;     // left rows, right rows, left rows that found a match, by partitions of the sort
 };
 
 struct qe_host_result {
@@ -505,6 +513,13 @@ enum DebugBit : int {
     kDbgGroupsOnDevice = 67108864,     // .. its groups are finished on the device whatever their number
 };
 inline bool debug_bit(const qe_ctx *ctx, DebugBit b) { return (ctx->opts.tuning[5] & b) != 0; }
+
+// the body of every qe_ctx_last_*_stats
+inline int32_t last_stats(const qe_ctx *ctx, Stats4 qe_ctx::*which, int64_t out[4]) {
+    if (!ctx || !out) return QE_ERR_INVALID_ARG;
+    for (int i = 0; i < 4; i++) out[i] = (ctx->*which).w[i];
+    return QE_OK;
+}
 
 }  // namespace qe
 

@@ -169,8 +169,7 @@ qe_join_table *build_table(qe_ctx *ctx, const qe_join_input *in, const int32_t *
     }
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->join_stats[0] = t->m;
-    ctx->join_stats[1] = ctx->join_stats[2] = ctx->join_stats[3] = 0;
+    ctx->join_stats.store(t->m, 0, 0, 0);
     return t.release();
 }
 
@@ -236,10 +235,7 @@ qe_result *probe_table(qe_ctx *ctx, const qe_join_table *t, const qe_join_input 
     for (int32_t i = 0; i < nbuild_out; i++) emit(t->build.cols[(size_t)build_out[i]], pa.brow_out, join_type == QE_JOIN_LEFT);
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->join_stats[0] = t->m;
-    ctx->join_stats[1] = n;
-    ctx->join_stats[2] = total;
-    ctx->join_stats[3] = (int64_t)(uint32_t)h_ctl[1];
+    ctx->join_stats.store(t->m, n, total, (int64_t)(uint32_t)h_ctl[1]);
     return res.release();
 }
 
@@ -272,11 +268,7 @@ int32_t qe_join_probe(qe_ctx *ctx, const qe_join_table *table, const qe_join_inp
     });
 }
 
-int32_t qe_ctx_last_join_stats(const qe_ctx *ctx, int64_t out[4]) {
-    if (!ctx || !out) return QE_ERR_INVALID_ARG;
-    for (int i = 0; i < 4; i++) out[i] = ctx->join_stats[i];
-    return QE_OK;
-}
+int32_t qe_ctx_last_join_stats(const qe_ctx *ctx, int64_t out[4]) { return last_stats(ctx, &qe_ctx::join_stats, out); }
 
 int32_t qe_batch_from_result(qe_ctx *ctx, const qe_result *result, qe_batch **out) {
     if (out) *out = nullptr;

@@ -1,7 +1,6 @@
 // qe_ordered.cpp -- host side of the ordered-set aggregates per group (kernels: qe_ordered.hip): one sort by
-// (group columns, argument) per distinct argument column with the ORDER BY driver, the window operator's boundary flags through
-// the sorted rows, then word ranks, compacted group and run starts, the first valid row of every group, and one small pass
-// per function.  Output columns that hold source values are the existing row gather over a per-group source-row list.
+// (group columns, argument) with its boundary flags (SortedRuns, qe_exec.h) per distinct argument column, then word ranks,
+// compacted group and run starts, the first valid row of every group, and one small pass per function.  Output columns that hold source values are the existing row gather over a per-group source-row list.
 #include <algorithm>
 #include <cmath>
 
@@ -72,7 +71,7 @@ qe_result *run_group_ordered(qe_ctx *ctx, const qe_result *src, const int32_t *g
             QE_HIP(hipStreamSynchronize(ctx->stream));
         }
         stats[1] = rows;
-        for (int i = 0; i < 4; i++) ctx->ordered_stats[i] = stats[i];
+        ctx->ordered_stats.store(stats);
         return res.release();
     }
 
@@ -95,30 +94,9 @@ qe_result *run_group_ordered(qe_ctx *ctx, const qe_result *src, const int32_t *g
         std::vector<qe_sort_key> keys;
         for (int32_t k = 0; k < ngroup; k++) keys.push_back({group_cols[k], 0});
         if (arg >= 0) keys.push_back({arg, 0});
-        const int32_t nkeys = (int32_t)keys.size();
-        SortDriver drv{ctx, ss, src, keys.data(), nkeys};
-        drv.prepare();
-        RadixBuffers rb(ss, n);
-        drv.sort(rb, true);
-        const uint32_t *perm = rb.sorted_rows();
-        WinFlagArgs fa{};
-        fa.nkeys = nkeys;
-        fa.npart = ngroup;
-        fa.n = n;
-        fa.pstart = pstart;
-        fa.peer = peer;
-        fa.npartitions = d_ngroups;
-        fa.perm = perm;
-        for (int32_t k = 0; k < nkeys; k++) {
-            const OutColumn &kc = src->cols[(size_t)keys[(size_t)k].column];
-            fa.type[k] = kc.type;
-            fa.data[k] = kc.data;
-            fa.validity[k] = (const unsigned long long *)kc.validity;
-            fa.ranks[k] = drv.d_ranks[(size_t)k];
-            fa.nranks[k] = drv.nranks[(size_t)k];
-        }
-        QE_HIP(hipMemsetAsync(d_ngroups, 0, 16, ctx->stream));
-        launch_win_flags(ctx->stream, fa);
+        SortedRuns runs(ctx, ss, src, keys.data(), (int32_t)keys.size());
+        const uint32_t *perm = runs.rows;
+        runs.flag(ngroup, pstart, peer, d_ngroups);
         // The groups of this sort: the count sizes the output (first sort) and must be the same in every sort.  The read-back
         // joins those the sort itself makes per key (SortDriver::varying).
         unsigned long long h_ngroups = 0;
@@ -126,8 +104,7 @@ qe_result *run_group_ordered(qe_ctx *ctx, const qe_result *src, const int32_t *g
         QE_HIP(hipGetLastError());
         QE_HIP(hipStreamSynchronize(ctx->stream));
         if (s_ == 0) {
-            G = (int64_t)h_ngroups;
-            if (G < 1 || G > n) fail(QE_ERR_INTERNAL, std::string(who) + ": " + std::to_string(G) + " groups of " + std::to_string(n) + " rows");
+            G = checked_runs(who, h_ngroups, "groups", n);
             res = new_result(ctx, G);
             add_schema(res.get(), G);
             gstart = (uint32_t *)sc.alloc((size_t)(G + 1) * 4);
@@ -138,10 +115,10 @@ qe_result *run_group_ordered(qe_ctx *ctx, const qe_result *src, const int32_t *g
                                       " groups, the first sort " + std::to_string(G));
         }
         stats[2]++;
-        stats[3] += drv.radix_passes;
+        stats[3] += runs.radix_passes();
 
         // ---- group starts; the key columns come from the first sort ----
-        bitmap_ranks(ctx->stream, (const uint64_t *)pstart, nullptr, n, pstart_prefix, sums, nullptr);
+        runs.rank_starts(pstart, pstart_prefix, sums);
         bitmap_positions(ctx->stream, (const uint64_t *)pstart, nullptr, n, pstart_prefix, gstart, G + 1, true);
         OsaGroups og{};
         og.n = n;
@@ -205,7 +182,7 @@ qe_result *run_group_ordered(qe_ctx *ctx, const qe_result *src, const int32_t *g
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));
     stats[1] = G;
-    for (int i = 0; i < 4; i++) ctx->ordered_stats[i] = stats[i];
+    ctx->ordered_stats.store(stats);
     return res.release();
 }
 
@@ -223,10 +200,6 @@ int32_t qe_result_group_ordered(qe_ctx *ctx, const qe_result *result, const int3
     return guarded(ctx, [&] { *out = run_group_ordered(ctx, result, group_cols, ngroup, fns, nfn); });
 }
 
-int32_t qe_ctx_last_ordered_stats(const qe_ctx *ctx, int64_t out[4]) {
-    if (!ctx || !out) return QE_ERR_INVALID_ARG;
-    for (int i = 0; i < 4; i++) out[i] = ctx->ordered_stats[i];
-    return QE_OK;
-}
+int32_t qe_ctx_last_ordered_stats(const qe_ctx *ctx, int64_t out[4]) { return last_stats(ctx, &qe_ctx::ordered_stats, out); }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // qe_sort.cpp -- host side of the sorts (kernels: qe_sort.hip): the radix-sort scratch every sorting operator
-// uses (RadixBuffers), the stable multi-key sort of a result's rows (SortDriver: ORDER BY and the window operator), and
+// uses (RadixBuffers), the stable multi-key sort of a result's rows (SortDriver), that sort with the boundary flags of its
+// runs (SortedRuns: the opening step of the window, the ordered-set aggregates, the set operations and the ASOF join), and
 // ORDER BY itself with its top-k selection.
 #include <algorithm>
 
@@ -85,6 +86,46 @@ void SortDriver::sort(RadixBuffers &rb, bool identity) {
     }
 }
 
+SortedRuns::SortedRuns(qe_ctx *ctx, PoolScratch &ss, const qe_result *src, const qe_sort_key *keys, int32_t nkeys)
+    : sorter{ctx, ss, src, keys, nkeys} {
+    if (nkeys == 0) return;
+    sorter.prepare();
+    RadixBuffers rb(ss, src->count);
+    sorter.sort(rb, true);
+    rows = rb.sorted_rows();
+}
+
+void SortedRuns::flag(int32_t npart, unsigned long long *pstart, unsigned long long *peer, unsigned long long *counter) {
+    WinFlagArgs fa{};
+    fa.nkeys = sorter.nkeys;
+    fa.npart = npart;
+    fa.n = sorter.src->count;
+    fa.pstart = pstart;
+    fa.peer = peer;
+    fa.npartitions = counter;
+    fa.perm = rows;
+    for (int32_t k = 0; k < sorter.nkeys; k++) {
+        const OutColumn &kc = sorter.src->cols[(size_t)sorter.keys[k].column];
+        fa.type[k] = kc.type;
+        fa.data[k] = kc.data;
+        fa.validity[k] = (const unsigned long long *)kc.validity;
+        fa.ranks[k] = sorter.d_ranks[(size_t)k];
+        fa.nranks[k] = sorter.nranks[(size_t)k];
+    }
+    QE_HIP(hipMemsetAsync(counter, 0, 16, sorter.ctx->stream));
+    launch_win_flags(sorter.ctx->stream, fa);
+}
+
+void SortedRuns::rank_starts(const unsigned long long *pstart, uint32_t *prefix, uint32_t *sums) {
+    bitmap_ranks(sorter.ctx->stream, (const uint64_t *)pstart, nullptr, sorter.src->count, prefix, sums, nullptr);
+}
+
+int64_t checked_runs(const char *who, unsigned long long count, const char *noun, int64_t n) {
+    const int64_t G = (int64_t)count;
+    if (G < 1 || G > n) fail(QE_ERR_INTERNAL, std::string(who) + ": " + std::to_string(G) + " " + noun + " of " + std::to_string(n) + " rows");
+    return G;
+}
+
 // ORDER BY on the device: OrderByOperator.open (operator/OrderByOperator.kt:9-15) sorts the materialised rows stably
 // with compareValues -- null first, Double.compareTo (-0.0 < 0.0, NaN greatest), String.compareTo (UTF-16 code units),
 // false < true.  Key images + stable LSD radix sort of (key, row id) + gather of every column (qe_sort.hip).
@@ -164,7 +205,7 @@ void order_by_impl(qe_ctx *ctx, const qe_result *src, const qe_sort_key *keys, i
         QE_HIP(hipGetLastError());
         QE_HIP(hipStreamSynchronize(ctx->stream));
     }
-    for (int i = 0; i < 4; i++) ctx->sort_stats[i] = stats[i];
+    ctx->sort_stats.store(stats);
     *out = res.release();
 }
 
@@ -188,10 +229,6 @@ int32_t qe_result_order_by_keys(qe_ctx *ctx, const qe_result *src, const qe_sort
     return guarded(ctx, [&] { order_by_impl(ctx, src, keys, nkeys, limit, "qe_result_order_by_keys", out); });
 }
 
-int32_t qe_ctx_last_sort_stats(const qe_ctx *ctx, int64_t out[4]) {
-    if (!ctx || !out) return QE_ERR_INVALID_ARG;
-    for (int i = 0; i < 4; i++) out[i] = ctx->sort_stats[i];
-    return QE_OK;
-}
+int32_t qe_ctx_last_sort_stats(const qe_ctx *ctx, int64_t out[4]) { return last_stats(ctx, &qe_ctx::sort_stats, out); }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // qe_window.cpp -- host side of the window operator (kernels: qe_window.hip): sort by (partition columns,
-// order keys) with the ORDER BY driver, gather every column, mark partition and peer starts, then one segmented scan per
+// order keys) and mark partition and peer starts (SortedRuns, qe_exec.h), gather every column, then one segmented scan per
 // function over the gathered columns.  A frame other than the running one is two scans kept as {value, count} pairs -- shared
 // by every function of the call that needs the same ones -- and one elementwise combine per function.
 #include <algorithm>
@@ -67,7 +67,7 @@ qe_result *run_window(qe_ctx *ctx, const char *who, int max_fn, const qe_result 
     const int64_t ntiles = (n + kWinTileRows - 1) / kWinTileRows;
     int64_t stats[4] = {n, 0, ntiles, n > 0 ? (ntiles + kWinTripTiles - 1) / kWinTripTiles : 0};
     if (n == 0) {
-        for (int i = 0; i < 4; i++) ctx->window_stats[i] = stats[i];
+        ctx->window_stats.store(stats);
         return res.release();
     }
 
@@ -75,34 +75,13 @@ qe_result *run_window(qe_ctx *ctx, const char *who, int max_fn, const qe_result 
     unsigned long long *pstart = (unsigned long long *)sc.alloc(bitmap_bytes(n));
     unsigned long long *peer = (unsigned long long *)sc.alloc(bitmap_bytes(n));
     unsigned long long *d_nparts = (unsigned long long *)sc.alloc(16);
-    QE_HIP(hipMemsetAsync(d_nparts, 0, 16, ctx->stream));
     unsigned long long h_nparts = 0;
     {
         // ---- sort + gather (skipped without keys: the columns are copied), then the boundary flags through the same row ids ----
         PoolScratch ss(ctx);
-        const int32_t nkeys = (int32_t)keys.size();
-        SortDriver drv{ctx, ss, src, keys.data(), nkeys};
-        WinFlagArgs fa{};
-        fa.nkeys = nkeys;
-        fa.npart = npart;
-        fa.n = n;
-        fa.pstart = pstart;
-        fa.peer = peer;
-        fa.npartitions = d_nparts;
-        if (nkeys > 0) {
-            drv.prepare();
-            RadixBuffers rb(ss, n);
-            drv.sort(rb, true);
-            gather_columns(ctx, src->cols, rb.sorted_rows(), n, res.get());
-            fa.perm = rb.sorted_rows();
-            for (int32_t k = 0; k < nkeys; k++) {
-                const OutColumn &kc = src->cols[(size_t)keys[(size_t)k].column];
-                fa.type[k] = kc.type;
-                fa.data[k] = kc.data;
-                fa.validity[k] = (const unsigned long long *)kc.validity;
-                fa.ranks[k] = drv.d_ranks[(size_t)k];
-                fa.nranks[k] = drv.nranks[(size_t)k];
-            }
+        SortedRuns runs(ctx, ss, src, keys.data(), (int32_t)keys.size());
+        if (runs.rows) {
+            gather_columns(ctx, src->cols, runs.rows, n, res.get());
         } else {
             for (size_t c = 0; c < src->cols.size(); c++) {
                 const OutColumn &s_ = src->cols[c];
@@ -110,7 +89,7 @@ qe_result *run_window(qe_ctx *ctx, const char *who, int max_fn, const qe_result 
                 if (s_.validity) QE_HIP(hipMemcpyAsync(res->cols[c].validity, s_.validity, bitmap_bytes(n), hipMemcpyDeviceToDevice, ctx->stream));
             }
         }
-        launch_win_flags(ctx->stream, fa);
+        runs.flag(npart, pstart, peer, d_nparts);
         QE_HIP(hipMemcpyAsync(&h_nparts, d_nparts, 8, hipMemcpyDeviceToHost, ctx->stream));
         QE_HIP(hipGetLastError());
         QE_HIP(hipStreamSynchronize(ctx->stream));   // the sort's scratch goes back to the pool here
@@ -259,7 +238,7 @@ qe_result *run_window(qe_ctx *ctx, const char *who, int max_fn, const qe_result 
     }
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 4; i++) ctx->window_stats[i] = stats[i];
+    ctx->window_stats.store(stats);
     return res.release();
 }
 
@@ -293,10 +272,6 @@ int32_t qe_result_window_frames(qe_ctx *ctx, const qe_result *result, const int3
     });
 }
 
-int32_t qe_ctx_last_window_stats(const qe_ctx *ctx, int64_t out[4]) {
-    if (!ctx || !out) return QE_ERR_INVALID_ARG;
-    for (int i = 0; i < 4; i++) out[i] = ctx->window_stats[i];
-    return QE_OK;
-}
+int32_t qe_ctx_last_window_stats(const qe_ctx *ctx, int64_t out[4]) { return last_stats(ctx, &qe_ctx::window_stats, out); }
 
 }  // extern "C"

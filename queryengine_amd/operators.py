@@ -11,6 +11,7 @@ There is no CPU evaluation here: expressions only ever run inside libqe_hip.so.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import struct
 from typing import Any, Callable, List, Optional, Sequence
@@ -61,6 +62,81 @@ def map(op: Operator, mapper: Callable[[List[Any]], Any]) -> list:   # noqa: A00
     return mapTo(op, [], mapper)
 
 
+def _is_gpu_operator(source: Any) -> bool:
+    """A source whose rows sit in HBM between its ``open()`` and ``close()``: it offers ``result()`` and ``ctx``."""
+    return hasattr(source, "result") and hasattr(source, "ctx")
+
+
+def _with_results(sources: Sequence[Operator], call: Callable[..., Any]) -> Any:
+    """``call(*[s.result() for s in sources])`` with the sources open: opened in order, one object once however often it is
+    listed, and closed in reverse order whether or not anything raises."""
+    with contextlib.ExitStack() as opened:
+        seen: list = []
+        for s in sources:
+            if not any(s is o for o in seen):
+                s.open()
+                opened.callback(s.close)
+                seen.append(s)
+        return call(*[s.result() for s in sources])
+
+
+class DeviceResultOperator(Operator):
+    """An operator that holds a device result.  When all its sources are GPU operators of one context its ``open()`` runs
+    ``_device_call`` on their results, the rows never leave HBM, and the operator offers ``result()`` and ``ctx`` itself, so an
+    operator on top works in HBM too; any other sources are drained and evaluated on the host by ``_rows_host()`` -- the
+    executable statement of the subclass's semantics, and the expectation of the device tests -- and the operator has no
+    ``ctx`` attribute at all.  A subclass ends its ``__init__`` with ``_set_sources``; ``_int_positions`` lists the row
+    positions (negative: from the end) whose device value is a count that travels as a float."""
+
+    _int_positions: Sequence[int] = ()
+
+    def _set_sources(self, *sources: Operator) -> None:
+        self._sources = sources
+        self._on_device = all(_is_gpu_operator(s) for s in sources) and all(s.ctx is sources[0].ctx for s in sources)
+        if self._on_device:
+            self.ctx = sources[0].ctx
+        self._result: Optional[E.Result] = None
+        self._iter = None
+
+    def _device_call(self, *results: E.Result) -> E.Result:
+        raise NotImplementedError
+
+    def _rows_host(self) -> List[List[Any]]:
+        raise NotImplementedError
+
+    def _device_rows(self):
+        cols = self._result.to_columns()       # at the first next(): an operator on top that takes result() never pays it
+        for i in range(len(cols[0]) if cols else 0):
+            row = [c.value(i) for c in cols]
+            for p in self._int_positions:
+                row[p] = int(row[p])
+            yield row
+
+    def open(self) -> None:
+        if self._on_device:
+            self._result = _with_results(self._sources, self._device_call)
+            self._iter = self._device_rows()
+        else:
+            self._iter = iter(self._rows_host())
+
+    def result(self) -> E.Result:
+        """The operator's columns in HBM (valid until close()); only when it ran on the device."""
+        if self._result is None:
+            raise RuntimeError("Operator not initialized")
+        return self._result
+
+    def next(self) -> Optional[List[Any]]:
+        if self._iter is None:
+            raise RuntimeError("Operator not opened")
+        return next(self._iter, None)
+
+    def close(self) -> None:
+        self._iter = None
+        if self._result is not None:
+            self._result.free()
+            self._result = None
+
+
 def _compare_key(value: Any):
     """Sort key with the order of Kotlin's ``compareValues`` on the boxed types of the engine: null first, then
     ``Double.compareTo`` (total order: -0.0 < 0.0, NaN greatest), ``String.compareTo`` (UTF-16 code units),
@@ -103,16 +179,15 @@ class OrderByOperator(Operator):
         self._sorted: Optional[E.Result] = None
 
     def open(self) -> None:
-        if hasattr(self.source, "result") and hasattr(self.source, "ctx"):
-            self.source.open()
-            try:
-                res = self.source.result()
+        if _is_gpu_operator(self.source):
+            ctx = self.source.ctx
+
+            def sort(res: E.Result) -> E.Result:
                 if self.keys is None and self.limit is None:
-                    self._sorted = self.source.ctx.order_by(res, self.index)
-                else:
-                    self._sorted = self.source.ctx.order_by_keys(res, self.keys or [(self.index, False)], self.limit)
-            finally:
-                self.source.close()
+                    return ctx.order_by(res, self.index)
+                return ctx.order_by_keys(res, self.keys or [(self.index, False)], self.limit)
+
+            self._sorted = _with_results([self.source], sort)
             cols = self._sorted.to_columns()
             n = self._sorted.count
             self._iter = ([c.value(i) for c in cols] for i in range(n))
@@ -151,7 +226,7 @@ def _join_key(values: Sequence[Any]):
     return tuple(key)
 
 
-class HashJoinOperator(Operator):
+class HashJoinOperator(DeviceResultOperator):
     """Equi-join of a probe source against a build source: ``probe_keys[i]`` pairs with ``build_keys[i]`` (column
     indices).  ``join_type`` is ``native.JOIN_INNER / JOIN_LEFT / JOIN_SEMI / JOIN_ANTI``.  A row is the listed probe
     columns followed by the listed build columns (``None`` = every column of that side; SEMI and ANTI have no build
@@ -179,34 +254,16 @@ class HashJoinOperator(Operator):
             raise ValueError("HashJoinOperator: a SEMI / ANTI join has no build columns")
         self.probe_out = None if probe_out is None else [int(c) for c in probe_out]
         self.build_out = None if build_out is None else [int(c) for c in build_out]
-        self._on_device = all(hasattr(s, "result") and hasattr(s, "ctx") for s in (probe, build)) and probe.ctx is build.ctx
-        if self._on_device:
-            self.ctx = probe.ctx
-        self._result: Optional[E.Result] = None
-        self._iter = None
+        self._set_sources(probe, build)
 
-    def _open_device(self) -> None:
-        self.probe.open()
+    def _device_call(self, pres: E.Result, bres: E.Result) -> E.Result:
+        probe_out = list(range(pres.ncols)) if self.probe_out is None else self.probe_out
+        build_out = (list(range(bres.ncols)) if self._pairs else []) if self.build_out is None else self.build_out
+        table = self.ctx.join_build(bres, self.build_keys)
         try:
-            self.build.open()
-            try:
-                pres, bres = self.probe.result(), self.build.result()
-                probe_out = list(range(pres.ncols)) if self.probe_out is None else self.probe_out
-                build_out = (list(range(bres.ncols)) if self._pairs else []) if self.build_out is None else self.build_out
-                table = self.ctx.join_build(bres, self.build_keys)
-                try:
-                    self._result = table.probe(pres, self.probe_keys, self.join_type, probe_out, build_out)
-                finally:
-                    table.free()
-            finally:
-                self.build.close()
+            return table.probe(pres, self.probe_keys, self.join_type, probe_out, build_out)
         finally:
-            self.probe.close()
-
-    def _device_rows(self):
-        cols = self._result.to_columns()       # at the first next(): an operator on top that takes result() never pays it
-        for i in range(len(cols[0]) if cols else 0):
-            yield [c.value(i) for c in cols]
+            table.free()
 
     def _rows_host(self) -> List[List[Any]]:
         build_rows = mapTo(self.build, [], lambda row: list(row))
@@ -243,30 +300,6 @@ class HashJoinOperator(Operator):
                 out.append(head + [None] * len(build_out))
         return out
 
-    def open(self) -> None:
-        if self._on_device:
-            self._open_device()
-            self._iter = self._device_rows()
-        else:
-            self._iter = iter(self._rows_host())
-
-    def result(self) -> E.Result:
-        """The joined columns in HBM (valid until close()); only when the join ran on the device."""
-        if self._result is None:
-            raise RuntimeError("Operator not initialized")
-        return self._result
-
-    def next(self) -> Optional[List[Any]]:
-        if self._iter is None:
-            raise RuntimeError("Operator not opened")
-        return next(self._iter, None)
-
-    def close(self) -> None:
-        self._iter = None
-        if self._result is not None:
-            self._result.free()
-            self._result = None
-
 
 def _window_min(a: float, b: float, want_max: bool) -> float:
     """MIN / MAX of two doubles as the aggregates decide them: NaN wins, -0.0 is below +0.0."""
@@ -279,7 +312,7 @@ def _window_min(a: float, b: float, want_max: bool) -> float:
     return b if _compare_key(b) < _compare_key(a) else a
 
 
-class WindowOperator(Operator):
+class WindowOperator(DeviceResultOperator):
     """Window functions over a source: every source row, sorted stably by ``partition_by`` (column indices, ascending) and
     then by ``order_by`` (``[(column, descending), ...]``, the comparator of ``OrderByOperator``), followed by one value
     per entry of ``functions`` = ``[(fn, column, offset), ...]`` or ``[(fn, column, offset, preceding, following), ...]``
@@ -324,21 +357,11 @@ class WindowOperator(Operator):
                 raise ValueError("WindowOperator: preceding and following are FRAME_UNBOUNDED or in [0, 2^31)")
             if not N.WIN_SUM <= fn <= N.WIN_AVG and fn not in (N.WIN_FIRST_VALUE, N.WIN_LAST_VALUE) and (preceding, following) != (0, 0):
                 raise ValueError("WindowOperator: the ranks and LAG / LEAD take no frame")
-        self._on_device = hasattr(source, "result") and hasattr(source, "ctx")
-        if self._on_device:
-            self.ctx = source.ctx
-        self._result: Optional[E.Result] = None
-        self._iter = None
+        self._int_positions = [k - len(self.functions) for k, f in enumerate(self.functions) if f[0] == N.WIN_COUNT]
+        self._set_sources(source)
 
-    def _device_rows(self):
-        cols = self._result.to_columns()
-        first = len(cols) - len(self.functions)
-        for i in range(len(cols[0]) if cols else 0):
-            row = [c.value(i) for c in cols]
-            for k, f in enumerate(self.functions):
-                if f[0] == N.WIN_COUNT:
-                    row[first + k] = int(row[first + k])
-            yield row
+    def _device_call(self, res: E.Result) -> E.Result:
+        return self.ctx.window(res, self.partition_by, self.order_by, self.functions)
 
     def _rows_host(self) -> List[List[Any]]:
         data = mapTo(self.source, [], lambda row: list(row))
@@ -426,40 +449,12 @@ class WindowOperator(Operator):
             return None
         return total if fn == N.WIN_SUM else total / count if fn == N.WIN_AVG else extreme
 
-    def open(self) -> None:
-        if self._on_device:
-            self.source.open()
-            try:
-                self._result = self.ctx.window(self.source.result(), self.partition_by, self.order_by, self.functions)
-            finally:
-                self.source.close()
-            self._iter = self._device_rows()
-        else:
-            self._iter = iter(self._rows_host())
-
-    def result(self) -> E.Result:
-        """The windowed columns in HBM (valid until close()); only when the source is a GPU operator."""
-        if self._result is None:
-            raise RuntimeError("Operator not initialized")
-        return self._result
-
-    def next(self) -> Optional[List[Any]]:
-        if self._iter is None:
-            raise RuntimeError("Operator not opened")
-        return next(self._iter, None)
-
-    def close(self) -> None:
-        self._iter = None
-        if self._result is not None:
-            self._result.free()
-            self._result = None
-
 
 def _same_bits(a: float, b: float) -> bool:
     return struct.pack("<d", a) == struct.pack("<d", b)
 
 
-class OrderedAggregateOperator(Operator):
+class OrderedAggregateOperator(DeviceResultOperator):
     """Ordered-set aggregates per group over a source: one row per group, the groups ASCENDING by the ``group_by`` columns
     under the comparator of ``OrderByOperator`` (``None`` first; not the insertion order of the GROUP BY operators; no column =
     the whole source is one group), the group columns followed by one value per entry of ``functions`` =
@@ -496,21 +491,11 @@ class OrderedAggregateOperator(Operator):
                 raise ValueError("OrderedAggregateOperator: unknown function")
             if fn in (N.OSA_PERCENTILE_CONT, N.OSA_PERCENTILE_DISC) and not 0.0 <= fraction <= 1.0:
                 raise ValueError("OrderedAggregateOperator: a percentile's fraction lies in [0, 1]")
-        self._on_device = hasattr(source, "result") and hasattr(source, "ctx")
-        if self._on_device:
-            self.ctx = source.ctx
-        self._result: Optional[E.Result] = None
-        self._iter = None
+        self._int_positions = [k - len(self.functions) for k, f in enumerate(self.functions) if f[0] == N.OSA_COUNT_DISTINCT]
+        self._set_sources(source)
 
-    def _device_rows(self):
-        cols = self._result.to_columns()
-        first = len(self.group_by)
-        for i in range(self._result.count):
-            row = [c.value(i) for c in cols]
-            for k, f in enumerate(self.functions):
-                if f[0] == N.OSA_COUNT_DISTINCT:
-                    row[first + k] = int(row[first + k])
-            yield row
+    def _device_call(self, res: E.Result) -> E.Result:
+        return self.ctx.group_ordered(res, self.group_by, self.functions)
 
     @staticmethod
     def _evaluate(fn: int, fraction: float, v: List[Any]):
@@ -563,36 +548,8 @@ class OrderedAggregateOperator(Operator):
             begin = end
         return out
 
-    def open(self) -> None:
-        if self._on_device:
-            self.source.open()
-            try:
-                self._result = self.ctx.group_ordered(self.source.result(), self.group_by, self.functions)
-            finally:
-                self.source.close()
-            self._iter = self._device_rows()
-        else:
-            self._iter = iter(self._rows_host())
 
-    def result(self) -> E.Result:
-        """The groups in HBM (valid until close()); only when the source is a GPU operator."""
-        if self._result is None:
-            raise RuntimeError("Operator not initialized")
-        return self._result
-
-    def next(self) -> Optional[List[Any]]:
-        if self._iter is None:
-            raise RuntimeError("Operator not opened")
-        return next(self._iter, None)
-
-    def close(self) -> None:
-        self._iter = None
-        if self._result is not None:
-            self._result.free()
-            self._result = None
-
-
-class SetOperator(Operator):
+class SetOperator(DeviceResultOperator):
     """UNION / INTERSECT / EXCEPT of two sources of one schema (``op`` one of ``native.SET_UNION / SET_INTERSECT / SET_EXCEPT``),
     with ``all=True`` the multiset form.  Two rows are equal when they compare equal on every column the way group keys do
     (``None`` equals ``None``, all NaNs are one value, -0.0 and 0.0 are two, strings by string).  Of a tuple that occurs cL times
@@ -619,12 +576,10 @@ class SetOperator(Operator):
             raise ValueError("SetOperator: all is False or True")
         self.left, self.right = left, right
         self.op, self.all = int(op), bool(all)
-        gpu = [hasattr(s, "result") and hasattr(s, "ctx") for s in (left, right)]
-        self._on_device = gpu[0] and gpu[1] and left.ctx is right.ctx
-        if self._on_device:
-            self.ctx = left.ctx
-        self._result: Optional[E.Result] = None
-        self._iter = None
+        self._set_sources(left, right)
+
+    def _device_call(self, lres: E.Result, rres: E.Result) -> E.Result:
+        return self.ctx.set_op(lres, rres, self.op, self.all)
 
     @staticmethod
     def _kept(op: int, all: bool, cl: int, cr: int) -> int:   # noqa: A002
@@ -665,51 +620,8 @@ class SetOperator(Operator):
             begin = end
         return out
 
-    def _open_device(self) -> None:
-        self.left.open()
-        try:
-            if self.right is self.left:
-                self._result = self.ctx.set_op(self.left.result(), self.left.result(), self.op, self.all)
-                return
-            self.right.open()
-            try:
-                self._result = self.ctx.set_op(self.left.result(), self.right.result(), self.op, self.all)
-            finally:
-                self.right.close()
-        finally:
-            self.left.close()
 
-    def _device_rows(self):
-        cols = self._result.to_columns()
-        for i in range(self._result.count):
-            yield [c.value(i) for c in cols]
-
-    def open(self) -> None:
-        if self._on_device:
-            self._open_device()
-            self._iter = self._device_rows()
-        else:
-            self._iter = iter(self._rows_host())
-
-    def result(self) -> E.Result:
-        """The kept rows in HBM (valid until close()); only when both sources are GPU operators."""
-        if self._result is None:
-            raise RuntimeError("Operator not initialized")
-        return self._result
-
-    def next(self) -> Optional[List[Any]]:
-        if self._iter is None:
-            raise RuntimeError("Operator not opened")
-        return next(self._iter, None)
-
-    def close(self) -> None:
-        self._iter = None
-        if self._result is not None:
-            self._result.free()
-            self._result = None
-
-
-class AsofJoinOperator(Operator):
+class AsofJoinOperator(DeviceResultOperator):
     """ASOF join: for every left row the ONE right row with an equal by tuple whose ``on`` value is nearest at or before it
     (``direction=native.ASOF_BACKWARD``) or at or after it (``ASOF_FORWARD``) -- for every trade the last quote of its symbol.
     ``left_by[i]`` pairs with ``right_by[i]`` (column indices, 0 to 7 of them; none: the whole input is one partition); by
@@ -750,12 +662,7 @@ class AsofJoinOperator(Operator):
         self.right_out = None if right_out is None else [int(c) for c in right_out]
         if self.left_out is not None and self.right_out is not None and not self.left_out + self.right_out:
             raise ValueError("AsofJoinOperator: no output column")
-        gpu = [hasattr(s, "result") and hasattr(s, "ctx") for s in (left, right)]
-        self._on_device = gpu[0] and gpu[1] and left.ctx is right.ctx
-        if self._on_device:
-            self.ctx = left.ctx
-        self._result: Optional[E.Result] = None
-        self._iter = None
+        self._set_sources(left, right)
 
     @staticmethod
     def _on_key(value: Any):
@@ -803,54 +710,11 @@ class AsofJoinOperator(Operator):
                 out.append(head + [None] * len(right_out))
         return out
 
-    def _join_device(self, lres: E.Result, rres: E.Result) -> E.Result:
+    def _device_call(self, lres: E.Result, rres: E.Result) -> E.Result:
         left_out = list(range(lres.ncols)) if self.left_out is None else self.left_out
         right_out = list(range(rres.ncols)) if self.right_out is None else self.right_out
         return self.ctx.asof_join(lres, rres, self.left_by, self.right_by, self.left_on, self.right_on, self.direction, self.strict,
                                   self.join_type, left_out, right_out)
-
-    def _open_device(self) -> None:
-        self.left.open()
-        try:
-            if self.right is self.left:
-                self._result = self._join_device(self.left.result(), self.left.result())
-                return
-            self.right.open()
-            try:
-                self._result = self._join_device(self.left.result(), self.right.result())
-            finally:
-                self.right.close()
-        finally:
-            self.left.close()
-
-    def _device_rows(self):
-        cols = self._result.to_columns()
-        for i in range(self._result.count):
-            yield [c.value(i) for c in cols]
-
-    def open(self) -> None:
-        if self._on_device:
-            self._open_device()
-            self._iter = self._device_rows()
-        else:
-            self._iter = iter(self._rows_host())
-
-    def result(self) -> E.Result:
-        """The joined columns in HBM (valid until close()); only when both sources are GPU operators."""
-        if self._result is None:
-            raise RuntimeError("Operator not initialized")
-        return self._result
-
-    def next(self) -> Optional[List[Any]]:
-        if self._iter is None:
-            raise RuntimeError("Operator not opened")
-        return next(self._iter, None)
-
-    def close(self) -> None:
-        self._iter = None
-        if self._result is not None:
-            self._result.free()
-            self._result = None
 
 
 class ColumnarScanOperator(Operator):

@@ -498,6 +498,38 @@ def test_operator_on_gpu_sources_matches_its_host_branch(gpu_ctx):
         assert_rows(dev, host, f"direction {direction} strict {strict} join {join_type}")
 
 
+@pytest.mark.parametrize("nl, nr", [(1, 0), (0, 1), (1, 1), (40, 24), (40, 25), (1000, 25)], ids=lambda v: str(v))
+def test_small_totals_against_the_host_operator(gpu_ctx, nl, nr):
+    """nl + nr = 1, 2, 64, 65 (the word edge of the partition-start bitmap) and 1025 (past one 1024-row block of the radix
+    histogram), by a nullable STRING column whose sides carry different dictionaries that share some strings."""
+    from queryengine_amd.operators import AsofJoinOperator, map as op_map
+    from test_setop_cpu import Rows, assert_rows
+    rng = np.random.default_rng(835 + nl + nr)
+
+    def side(n, dictionary):
+        valid = rng.random(n) > 0.2 if n else None
+        if n > 1:
+            valid[:2] = [True, False]       # never all ones: the bitmap stays
+        return [Column(S, rng.integers(0, len(dictionary), n).astype(np.int32), valid, dictionary), on_column(I64, rng, n, 6, 0.0),
+                Column(I64, np.arange(n, dtype=np.int64))]
+    lcols, rcols = side(nl, ["m", "b", "zz", "a"]), side(nr, ["a", "q", "zz", "c"])
+    boxed = lambda cols, n: [[c.value(i) for c in cols] for i in range(n)]      # noqa: E731
+    lrows, rrows = boxed(lcols, nl), boxed(rcols, nr)
+    pair = Pair(gpu_ctx, lcols, rcols)
+    try:
+        for direction, strict, join_type in FORMS:
+            host = op_map(AsofJoinOperator(Rows(lrows), Rows(rrows), [0], [0], 1, 1, direction, strict, join_type, right_out=[0, 1, 2]), list)
+            out = gpu_ctx.asof_join(pair.lres, pair.rres, [0], [0], 1, 1, direction, strict, join_type, [0, 1, 2], [0, 1, 2])
+            try:
+                assert_rows(boxed(out.to_columns(), out.count), host, f"nl {nl} nr {nr} direction {direction} strict {strict} join {join_type}")
+                assert gpu_ctx.last_asof_stats() == {"left_rows": nl, "right_rows": nr, "matched": sum(1 for row in host if row[5] is not None),
+                                                     "partitions": len({row[0] for row in lrows + rrows})}
+            finally:
+                out.free()
+    finally:
+        pair.free()
+
+
 # ---- 10. the errors that need a result to look at -----------------------------------------------------------------------------------
 def test_invalid_arguments(gpu_ctx):
     ctx = gpu_ctx

@@ -322,6 +322,38 @@ def test_operator_on_gpu_sources_matches_its_host_branch(gpu_ctx):
         assert_rows(dev, host, f"{NAMES[op]} all {all_}")
 
 
+@pytest.mark.parametrize("nl, nr", [(1, 0), (0, 1), (1, 1), (40, 24), (40, 25), (600, 425)], ids=lambda v: str(v))
+def test_small_totals_against_the_host_operator(gpu_ctx, nl, nr):
+    """nl + nr = 1, 2, 64, 65 (the word edge of the tuple-start bitmap) and 1025 (past one 1024-row block of the radix
+    histogram), over a nullable STRING column whose sides carry different dictionaries that share some strings."""
+    from queryengine_amd.operators import SetOperator, map as op_map
+    from test_setop_cpu import Rows, assert_rows
+    rng = np.random.default_rng(575 + nl + nr)
+
+    def side(n, dictionary):
+        valid = rng.random(n) > 0.2 if n else None
+        if n > 1:
+            valid[:2] = [True, False]       # never all ones: the bitmap stays
+        return [Column(S, rng.integers(0, len(dictionary), n).astype(np.int32), valid, dictionary), Column(I32, rng.integers(0, 3, n).astype(np.int32))]
+    lcols, rcols = side(nl, ["m", "b", "zz", "a"]), side(nr, ["a", "q", "zz", "c"])
+    boxed = lambda cols, n: [[c.value(i) for c in cols] for i in range(n)]      # noqa: E731
+    lbatch, lres = build(gpu_ctx, lcols)
+    rbatch, rres = build(gpu_ctx, rcols)
+    try:
+        tuples = len(op_map(SetOperator(Rows(boxed(lcols, nl)), Rows(boxed(rcols, nr)), U), list))
+        for op, all_ in FORMS:
+            host = op_map(SetOperator(Rows(boxed(lcols, nl)), Rows(boxed(rcols, nr)), op, all_), list)
+            out = gpu_ctx.set_op(lres, rres, op, all_)
+            try:
+                assert_rows(boxed(out.to_columns(), out.count), host, f"nl {nl} nr {nr} {NAMES[op]} all {all_}")
+                assert gpu_ctx.last_set_stats() == {"left_rows": nl, "right_rows": nr, "tuples": 0 if (op == U and all_) else tuples,
+                                                    "translated_columns": 1}
+            finally:
+                out.free()
+    finally:
+        lres.free(); rres.free(); lbatch.free(); rbatch.free()
+
+
 # ---- 9. determinism ------------------------------------------------------------------------------------------------------------
 def test_the_same_bytes_on_every_run_and_on_a_fresh_context(gpu_ctx):
     rng = np.random.default_rng(580)
