@@ -692,6 +692,75 @@ int32_t qe_result_asof_join(qe_ctx *ctx, const qe_result *left, const qe_result 
  * rows at all) */
 int32_t qe_ctx_last_asof_stats(const qe_ctx *ctx, int64_t out[4]);
 
+/* ---- range join of two results ----------------------------------------------------------------------------------
+ * For every left row ALL right rows of the same by tuple whose `on` value lies in the left row's interval [lo, hi]: all quotes
+ * in the five seconds before a trade, all events inside a session, all readings inside a calibration window, a value put into
+ * its bin.  The hash join (qe_join_build / qe_join_probe) matches on equality only and walks the matches of one probe row with
+ * one lane; the ASOF join returns at most one right row per left row.  The reference has no join at all (Query.g4 reads one
+ * table).
+ *
+ * Keys: 0 <= nby <= 7 (the by columns and one value column are the sort's 8 keys).  By column i of the left pairs with by
+ * column i of the right; the two have the same type, any of the five.  Two by tuples are equal as hash-join keys are
+ * (Double.equals: every NaN is one value, -0.0 is not 0.0; STRING compares by string, the sides may carry different
+ * dictionaries), and a NULL in any by column, on either side, matches nothing.  nby == 0: the whole input is one partition.
+ *
+ * Interval: left_lo and left_hi (columns of the left) and right_on (a column of the right) are DOUBLE, INT64 or INT32, all three
+ * of one type, and are compared in that type under the comparator of qe_result_order_by_keys: Double.compareTo for DOUBLE
+ * (-0.0 < 0.0, NaN greatest, all NaNs equal), integer order for the integer types -- INT64 values beyond 2^53 never go through a
+ * double.  Right row r matches left row l when the by tuples are equal, cmp(on(r), lo(l)) >= 0 (> 0 when lo_strict) and
+ * cmp(on(r), hi(l)) <= 0 (< 0 when hi_strict).  A NULL lo, hi or on matches nothing; an empty interval (lo above hi, or lo
+ * equal to hi with a strict end) matches nothing.  left_lo == left_hi (the same column) is allowed: with no strict end it is
+ * equality on the value.  The library does no arithmetic on the bounds: a caller derives them with a projection such as t - 5,
+ * t + 5 through qe_filter_project and passes the result in.
+ *
+ * Join types (the values of the hash join's enum).  QE_JOIN_INNER: one row per (left row, matching right row).  QE_JOIN_LEFT:
+ * the same, and one row in its place for every left row without a match, every right column of it NULL (validity 0, value
+ * zero).  QE_JOIN_SEMI: every left row with at least one match, once.  QE_JOIN_ANTI: every left row without one (a NULL key
+ * counts as no match).  SEMI and ANTI take no right columns (nright_out == 0).
+ *
+ * Order: left rows come out in input order; inside one left row the matches ascend by on(r) under the comparator, ties in
+ * ascending right row index.  So with left_lo == left_hi, no strict end, nby == 0 and a key without NULLs the pairs and their
+ * order are exactly those of qe_join_probe with the left as probe side.
+ *
+ * Columns: the listed left columns, then the listed right columns.  A column may be listed twice and either list may be empty,
+ * but there is at least one output column.  A STRING column carries its source's dictionary (merged dictionaries are scratch
+ * for the keys only); nullability is the source's, and under QE_JOIN_LEFT every right column is nullable.  `left` and `right`
+ * may be the same handle.
+ *
+ * Determinism: the same inputs give the same bytes on every run and every context.  No atomic feeds a result byte (the one
+ * atomic is an integer max for the stats).
+ *
+ * Sizes: counts and offsets of the output are 64-bit throughout; the output's size is read back once, as in the hash join,
+ * together with the stats.
+ *
+ * Limits and errors (*out = NULL): QE_ERR_INVALID_ARG for a null pointer (left_by / right_by may be null when nby == 0, a column
+ * list when its count is 0), nby outside 0..7, a strict flag other than 0 or 1, a join_type outside the four, a negative column
+ * count, no output column, right columns with SEMI or ANTI -- these are checked before either result is read -- a column out of
+ * range, paired by columns of different types, a value column that is not DOUBLE, INT64 or INT32, value columns whose types
+ * differ among the three, a STRING by column without a dictionary; QE_ERR_UNSUPPORTED for left rows + right rows > 2^32 - 2;
+ * QE_ERR_HIP on a planning-only context; QE_ERR_OOM when scratch or output does not fit.  Zero rows on either side is an
+ * ordinary input and returns the full schema.
+ *
+ * Lifetime and reuse: the output owns its buffers and shares the dictionaries; both inputs may be freed once the call returns.
+ * The output is an ordinary result (qe_batch_from_result, qe_result_order_by_keys, another range join, ..).
+ *
+ * How: two stable sorts over the concatenated key columns of both sides (right STRING codes through the set operations'
+ * translation table), one with lo and one with hi as the left rows' value next to the right rows' on; the order of the
+ * concatenation lets ties fall the way the two ends are defined.  In each sort a left row reads off its ORDINAL, the number of
+ * right rows with a whole key before it.  Those right rows stand in the same order in both sorts, so the two ordinals index one
+ * list and the matches of a left row are the entries between them.  A 64-bit scan of the per-row counts gives every left row
+ * its first output row, and a load-balanced expansion -- a workgroup per tile of consecutive OUTPUT rows, a search per output
+ * row, no lane walking one left row's matches -- writes the row pairs for the row gather every operator uses. */
+int32_t qe_result_range_join(qe_ctx *ctx, const qe_result *left, const qe_result *right,
+                             const int32_t *left_by, const int32_t *right_by, int32_t nby,
+                             int32_t left_lo, int32_t left_hi, int32_t right_on,
+                             int32_t lo_strict, int32_t hi_strict, int32_t join_type,   /* QE_JOIN_INNER / LEFT / SEMI / ANTI */
+                             const int32_t *left_out, int32_t nleft_out,
+                             const int32_t *right_out, int32_t nright_out, qe_result **out);
+/* what the last qe_result_range_join of this context did: out[0] left rows, out[1] right rows, out[2] output rows, out[3] the
+ * most matches any one left row has */
+int32_t qe_ctx_last_range_stats(const qe_ctx *ctx, int64_t out[4]);
+
 /* zero-copy: a batch whose columns ARE the result's (not owned; the result must outlive the batch).  Same columns, same
  * validity (NULL where the result has none), same dictionaries, nrows = the result's count (zero rows: a zero-row batch).
  * The batch goes into qe_filter_project / qe_filter_aggregate / qe_filter_groupby like any other: that is how a join is

@@ -84,6 +84,13 @@ internal object QeNative {
     val qe_result_asof_join = handle("qe_result_asof_join", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT,
         JAVA_INT, JAVA_INT, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS)
     val qe_ctx_last_asof_stats = handle("qe_ctx_last_asof_stats", JAVA_INT, ADDRESS, ADDRESS)         // ctx, long[4]
+    // ---- range join of two results: lo_strict / hi_strict 0 / 1 exclude that end; join_type 0 INNER, 1 LEFT, 2 SEMI, 3 ANTI ----
+    // ctx, left, right, int[] left_by, int[] right_by, nby (0..7), left_lo, left_hi, right_on, lo_strict, hi_strict, join_type, int[] left_out,
+    // nleft_out, int[] right_out, nright_out (0 for SEMI / ANTI), qe_result** -> status: per left row all right rows of its by tuple with on in
+    // [lo, hi], in left row order, the matches of one left row ascending by on
+    val qe_result_range_join = handle("qe_result_range_join", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT,
+        JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS)
+    val qe_ctx_last_range_stats = handle("qe_ctx_last_range_stats", JAVA_INT, ADDRESS, ADDRESS)       // ctx, long[4]: left rows, right rows, output rows, longest
     // ctx, result, qe_batch** -> status: a batch whose columns ARE the result's (zero copy): the input of the next plan
     val qe_batch_from_result = handle("qe_batch_from_result", JAVA_INT, ADDRESS, ADDRESS, ADDRESS)
 

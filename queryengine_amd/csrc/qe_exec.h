@@ -10,7 +10,7 @@
 //                    the device group finish share with it, and that sort with the boundary flags of its runs (SortedRuns):
 //                    how the four sorted-run operators below begin
 //   qe_comm.cpp      the RCCL exchange step, the concatenation of results, and the two-sided concatenation with merged
-//                    dictionaries (concat_two_sided) that the set operations and the ASOF join begin with
+//                    dictionaries (concat_two_sided) that the set operations, the ASOF join and the range join begin with
 //   qe_join.cpp      the hash equi-join of two device-resident sides, a result as the next plan's batch
 //   qe_window.cpp    window functions over a result: sorted runs, the row gather, the segmented scans
 //   qe_ordered.cpp   ordered-set aggregates per group (quantiles, COUNT DISTINCT, MODE): sorted runs per argument column,
@@ -19,6 +19,9 @@
 //                    a keep bitmap from per-tuple counts of the two sides, the row gather
 //   qe_asof.cpp      the ASOF join of two results: the key columns of the two sides as one, sorted runs over (by.., on),
 //                    the nearest eligible right position per left row, the row gather
+//   qe_range.cpp     the range join of two results: the key columns of the two sides as one, sorted runs over (by.., lo) and
+//                    over (by.., hi), two ordinals per left row, a 64-bit scan of the counts, the load-balanced expansion
+//                    into row pairs, the row gather
 #pragma once
 
 #include <memory>

@@ -448,6 +448,7 @@ struct qe_ctx {
     qe::Stats4 ordered_stats;  // rows, groups, sorts run, radix passes of those sorts
     qe::Stats4 set_stats;      // left rows, right rows, distinct tuples the sort found, STRING columns translated
     qe::Stats4 asof_stats;     // left rows, right rows, left rows that found a match, by partitions of the sort
+    qe::Stats4 range_stats;    // left rows, right rows, output rows, most matches of one left row
 };
 
 struct qe_host_result {

@@ -287,6 +287,50 @@ void launch_asof_pick(hipStream_t s, const AsofPickArgs &a);
 // the LEFT form's own side)
 void launch_asof_matched(hipStream_t s, const uint32_t *match, int64_t nleft, unsigned long long *matched, uint32_t *identity);
 
+// ---- range join over two concatenated, sorted key sets (qe_range.hip) ----
+// grid cap, in blocks of 256 threads, of its three kernels (524 288 rows a sweep of the two lane-per-row kernels)
+constexpr int kRangeBlocks = 2048;
+// consecutive output rows that one workgroup of the expansion owns at a time
+constexpr int kRangeExpandTile = 2048;
+// One sort's ordinals.  The row at sorted position j has k = set bits of `right` below j eligible right rows before it.  A left
+// row l writes ord[l] = k, or 0xFFFFFFFF when its bit of `eligible` is 0 -- every left row once.  An eligible right row r
+// writes rlist[k] = r (rlist null: not wanted), so rlist becomes the eligible right rows in sorted order; it has room for the
+// n - nleft right rows.  eligible / right: the bitmaps of launch_asof_eligible, right_prefix: the word ranks of `right`
+struct RangeOrdinalArgs {
+    AsofSides s;
+    long long nleft;
+    const unsigned long long *eligible, *right;
+    const unsigned int *right_prefix;
+    unsigned int *ord, *rlist;
+};
+void launch_range_ordinals(hipStream_t s, const RangeOrdinalArgs &a);
+// Per left row l < nleft: cnt[l] = ord_hi[l] - ord_lo[l] when both ordinals are there and the difference is positive, else 0;
+// emit[l] (emit null: not wanted) = the output rows of l, cnt[l] or (left_join) max(cnt[l], 1); bit l of keep = (cnt[l] != 0) !=
+// (anti != 0), whole words, the bits past nleft 0; *longest (zeroed by the caller) = max cnt[l], by an integer atomic max
+struct RangeCountArgs {
+    long long nleft;
+    int left_join, anti;
+    const unsigned int *ord_lo, *ord_hi;
+    unsigned int *cnt;
+    long long *emit;
+    unsigned long long *keep;
+    unsigned int *longest;
+};
+void launch_range_counts(hipStream_t s, const RangeCountArgs &a);
+// The load-balanced expansion: output row o < total belongs to the last emitting left row e with eoff[e] <= o; with l = erow[e]
+// (erow null: l = e) and k = o - eoff[e] it writes lrow[o] = l and rrow[o] = cnt[l] ? rlist[ord_lo[l] + k] : 0xFFFFFFFF.  eoff:
+// the first output row of each of the nemit emitting left rows, strictly ascending from 0, so a tile of kRangeExpandTile output
+// rows meets at most kRangeExpandTile + 1 of them: a workgroup stages those in LDS and every lane searches there
+struct RangeExpandArgs {
+    long long total, nemit, nleft, nright;
+    const long long *eoff;
+    const unsigned int *erow;
+    const unsigned int *cnt, *ord_lo;       // per left row
+    const unsigned int *rlist;              // nright entries
+    unsigned int *lrow, *rrow;
+};
+void launch_range_expand(hipStream_t s, const RangeExpandArgs &a);
+
 // ---- gathers through u32 row ids (qe_kernels.hip): ORDER BY, window, join, per-node ----
 // grid caps, in blocks of 256 threads: every caller's, and the join's output columns (with the narrow cap the probe was 0.4 to
 // 0.6 % slower than before in every interleaved run, with the wide one it is not: profiles/result_builder_refactor_summary.txt)

@@ -289,6 +289,29 @@ class Context:
         N.check(self.handle, self._lib.qe_ctx_last_asof_stats(self.handle, out))
         return {"left_rows": int(out[0]), "right_rows": int(out[1]), "matched": int(out[2]), "partitions": int(out[3])}
 
+    def range_join(self, left: "Result", right: "Result", left_by: Sequence[int], right_by: Sequence[int], left_lo: int, left_hi: int,
+                   right_on: int, lo_strict: bool = False, hi_strict: bool = False, join_type: int = N.JOIN_INNER,
+                   left_out: Sequence[int] = (), right_out: Sequence[int] = ()) -> "Result":
+        """qe_result_range_join: per left row ALL right rows with an equal by tuple (as hash-join keys are equal; a NULL matches
+        nothing) whose `on` value lies in [lo, hi] of the left row (`lo_strict` / `hi_strict` exclude that end; compared like
+        order_by_keys compares, a NULL bound or `on` matches nothing).  The listed left columns, then the listed right columns:
+        left rows in input order, the matches of one left row ascending by `on`, ties in right row order.  JOIN_INNER the pairs;
+        JOIN_LEFT also a row with NULL right columns for a left row without a match; JOIN_SEMI / JOIN_ANTI the left rows with /
+        without a match, once, and no right columns."""
+        h = C.c_void_p()
+        N.check(self.handle, self._lib.qe_result_range_join(
+            self.handle, left.handle, right.handle, _i32_array(left_by), _i32_array(right_by), len(left_by), int(left_lo), int(left_hi),
+            int(right_on), int(lo_strict), int(hi_strict), int(join_type), _i32_array(left_out), len(left_out), _i32_array(right_out),
+            len(right_out), C.byref(h)))
+        return Result(self, h)
+
+    def last_range_stats(self) -> dict:
+        """qe_ctx_last_range_stats: left rows, right rows, output rows and the most matches any one left row has, of the last
+        range_join()."""
+        out = (C.c_int64 * 4)()
+        N.check(self.handle, self._lib.qe_ctx_last_range_stats(self.handle, out))
+        return {"left_rows": int(out[0]), "right_rows": int(out[1]), "output_rows": int(out[2]), "longest": int(out[3])}
+
     def concat(self, parts: Sequence["Result"]) -> "Result":
         """qe_result_concat: results of this device, concatenated in the given order."""
         arr = (C.c_void_p * max(1, len(parts)))(*[p.handle for p in parts])

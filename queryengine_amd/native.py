@@ -42,6 +42,8 @@ SET_UNION, SET_INTERSECT, SET_EXCEPT = range(3)   # qe_result_set_op (DESIGN.md 
 SETOP_BLOCKS = 2048                          # grid cap of its two bitmap kernels in blocks of 256 lanes (kSetopBlocks)
 ASOF_BACKWARD, ASOF_FORWARD = range(2)       # qe_result_asof_join
 ASOF_BLOCKS = 2048                           # grid cap of its three kernels in blocks of 256 lanes (kAsofBlocks)
+RANGE_BLOCKS = 2048                          # qe_result_range_join: grid cap of its three kernels (kRangeBlocks)
+RANGE_EXPAND_TILE = 2048                     # output rows one workgroup of its expansion owns at a time (kRangeExpandTile)
 
 
 class QeError(RuntimeError):
@@ -183,6 +185,10 @@ SYMBOLS = [
                                         C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                         C.POINTER(_P)]),
     ("qe_ctx_last_asof_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
+    ("qe_result_range_join", C.c_int32, [_P, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
+                                         C.c_int32, C.POINTER(_P)]),
+    ("qe_ctx_last_range_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_batch_from_result", C.c_int32, [_P, _P, C.POINTER(_P)]),
     ("qe_comm_unique_id", C.c_int32, [_P, _P]),
     ("qe_comm_init", C.c_int32, [_P, C.c_int32, C.c_int32, _P]),

@@ -717,6 +717,113 @@ class AsofJoinOperator(DeviceResultOperator):
                                   self.join_type, left_out, right_out)
 
 
+class RangeJoinOperator(DeviceResultOperator):
+    """Range join: for every left row ALL right rows with an equal by tuple whose ``on`` value lies in the left row's interval
+    ``[lo, hi]`` -- all quotes in the five seconds before a trade.  ``left_by[i]`` pairs with ``right_by[i]`` (column indices, 0
+    to 7 of them; none: the whole input is one partition); by tuples are equal as hash-join keys are (every NaN one value, -0.0
+    and 0.0 two, strings by string) and a ``None`` in a by column, in ``lo``, ``hi`` or ``on`` matches nothing.  ``left_lo`` and
+    ``left_hi`` are columns of the left (they may be the same column), ``right_on`` one of the right; all three are numeric, of
+    one type, and compare like ``OrderByOperator`` compares (``Double.compareTo``; integers exactly).  ``lo_strict`` /
+    ``hi_strict`` exclude that end; an empty interval matches nothing.
+
+    A row is the listed left columns followed by the listed right columns (``None`` = every column of that side; SEMI and ANTI
+    have no right columns).  Left rows come in input order, the matches of one left row ascending by ``on``, ties in right row
+    order: ``native.JOIN_INNER`` the pairs, ``JOIN_LEFT`` also a row with every right column ``None`` for a left row without a
+    match, ``JOIN_SEMI`` / ``JOIN_ANTI`` the left rows with / without a match, once.  ``left`` and ``right`` may be the same
+    operator; it is then drained once.  The reference has no join (Query.g4 reads one table).
+
+    When both sources are GPU operators of one context (``result()`` and ``ctx``) the rows never leave HBM
+    (qe_result_range_join) and the operator offers ``result()`` and ``ctx`` itself.  Any other pair is drained and joined on the
+    host by a plain nested loop over ``_join_key`` and ``_compare_key`` -- the executable statement of the semantics, written
+    for clarity, and the expectation of the device tests."""
+
+    def __init__(self, left: Operator, right: Operator, left_by: Sequence[int], right_by: Sequence[int], left_lo: int, left_hi: int,
+                 right_on: int, lo_strict: bool = False, hi_strict: bool = False, join_type: int = N.JOIN_INNER,
+                 left_out: Optional[Sequence[int]] = None, right_out: Optional[Sequence[int]] = None):
+        if left is None or right is None:
+            raise ValueError("RangeJoinOperator: two sources")
+        self.left, self.right = left, right
+        self.left_by, self.right_by = [int(c) for c in left_by], [int(c) for c in right_by]
+        if len(self.left_by) > 7 or len(self.left_by) != len(self.right_by):
+            raise ValueError("RangeJoinOperator: 0 to 7 by columns, as many on the left as on the right")
+        self.left_lo, self.left_hi, self.right_on = int(left_lo), int(left_hi), int(right_on)
+        if lo_strict not in (False, True, 0, 1) or hi_strict not in (False, True, 0, 1):
+            raise ValueError("RangeJoinOperator: a strict flag is False or True")
+        if isinstance(join_type, bool) or join_type not in (N.JOIN_INNER, N.JOIN_LEFT, N.JOIN_SEMI, N.JOIN_ANTI):
+            raise ValueError("RangeJoinOperator: unknown join type")
+        self.lo_strict, self.hi_strict, self.join_type = bool(lo_strict), bool(hi_strict), int(join_type)
+        self._pairs = self.join_type in (N.JOIN_INNER, N.JOIN_LEFT)
+        if not self._pairs and right_out:
+            raise ValueError("RangeJoinOperator: a SEMI / ANTI join has no right columns")
+        self.left_out = None if left_out is None else [int(c) for c in left_out]
+        self.right_out = None if right_out is None else [int(c) for c in right_out]
+        no_right_column = not self._pairs or (self.right_out is not None and not self.right_out)
+        if self.left_out is not None and not self.left_out and no_right_column:
+            raise ValueError("RangeJoinOperator: no output column")
+        self._set_sources(left, right)
+
+    @staticmethod
+    def _value_key(value: Any):
+        if value is not None and (isinstance(value, bool) or not isinstance(value, (int, float))):
+            raise ValueError("RangeJoinOperator: the value columns are numeric")
+        return None if value is None else _compare_key(value)
+
+    def _matches(self, row: List[Any], right_rows: List[List[Any]]) -> List[List[Any]]:
+        """The right rows that `row` matches, ascending by ``on``, ties in right row order."""
+        key = _join_key([row[c] for c in self.left_by])
+        lo, hi = self._value_key(row[self.left_lo]), self._value_key(row[self.left_hi])
+        if lo is not None and hi is not None and isinstance(row[self.left_lo], float) != isinstance(row[self.left_hi], float):
+            raise ValueError("RangeJoinOperator: the value columns differ in type")
+        if key is None or lo is None or hi is None:
+            return []
+        found = []
+        for r in right_rows:                                   # in right row order
+            on = self._value_key(r[self.right_on])
+            if on is None or _join_key([r[c] for c in self.right_by]) != key:
+                continue
+            if isinstance(r[self.right_on], float) != isinstance(row[self.left_lo], float):
+                raise ValueError("RangeJoinOperator: the value columns differ in type")
+            if (on > lo or (on == lo and not self.lo_strict)) and (on < hi or (on == hi and not self.hi_strict)):
+                found.append((on, r))
+        found.sort(key=lambda item: item[0])                   # stable: ties stay in right row order
+        return [r for _, r in found]
+
+    def _rows_host(self) -> List[List[Any]]:
+        left_rows = mapTo(self.left, [], lambda row: list(row))
+        right_rows = left_rows if self.right is self.left else mapTo(self.right, [], lambda row: list(row))
+        right_out = self.right_out
+        if right_out is None:
+            if not self._pairs:
+                right_out = []
+            elif right_rows:
+                right_out = list(range(len(right_rows[0])))
+            elif self.join_type == N.JOIN_LEFT and left_rows:
+                raise ValueError("RangeJoinOperator: right_out must be given when a LEFT join's right source yields no row")
+            else:
+                right_out = []
+        out = []
+        for row in left_rows:
+            head = [row[c] for c in (range(len(row)) if self.left_out is None else self.left_out)]
+            matches = self._matches(row, right_rows)
+            if self.join_type == N.JOIN_SEMI:
+                if matches:
+                    out.append(head)
+            elif self.join_type == N.JOIN_ANTI:
+                if not matches:
+                    out.append(head)
+            elif matches:
+                out.extend(head + [m[c] for c in right_out] for m in matches)
+            elif self.join_type == N.JOIN_LEFT:
+                out.append(head + [None] * len(right_out))
+        return out
+
+    def _device_call(self, lres: E.Result, rres: E.Result) -> E.Result:
+        left_out = list(range(lres.ncols)) if self.left_out is None else self.left_out
+        right_out = (list(range(rres.ncols)) if self._pairs else []) if self.right_out is None else self.right_out
+        return self.ctx.range_join(lres, rres, self.left_by, self.right_by, self.left_lo, self.left_hi, self.right_on, self.lo_strict,
+                                   self.hi_strict, self.join_type, left_out, right_out)
+
+
 class ColumnarScanOperator(Operator):
     """Scan leaf over a ColumnarTable (replaces MemorySourceOperator.kt:5-36).
 
