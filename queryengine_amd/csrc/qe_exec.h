@@ -17,11 +17,13 @@
 //                    then ranks, compaction and picks over the sorted rows
 //   qe_setop.cpp     UNION / INTERSECT / EXCEPT [ALL] of two results: the two sides as one, sorted runs over every column,
 //                    a keep bitmap from per-tuple counts of the two sides, the row gather
-//   qe_asof.cpp      the ASOF join of two results: the key columns of the two sides as one, sorted runs over (by.., on),
-//                    the nearest eligible right position per left row, the row gather
-//   qe_range.cpp     the range join of two results: the key columns of the two sides as one, sorted runs over (by.., lo) and
-//                    over (by.., hi), two ordinals per left row, a 64-bit scan of the counts, the load-balanced expansion
-//                    into row pairs, the row gather
+//   qe_two_sided.cpp what the joins of two results share: the checks of their arguments, the key sort of the two sides as
+//                    one (TwoSidedKeys: concat_two_sided, sorted runs over (by.., value), the eligible and the right rows), and
+//                    the output step (emit_joined)
+//   qe_asof.cpp      the ASOF join of two results: one key sort over (by.., on), the nearest eligible right position per
+//                    left row, the output step
+//   qe_range.cpp     the range join of two results: a key sort over (by.., lo) and one over (by.., hi), two ordinals per left
+//                    row, a 64-bit scan of the counts, the load-balanced expansion into row pairs, the output step
 #pragma once
 
 #include <memory>
@@ -30,6 +32,7 @@
 #include <vector>
 
 #include "qe_internal.h"
+#include "qe_kernels.h"
 
 namespace qe {
 #pragma GCC visibility push(hidden)
@@ -181,6 +184,75 @@ struct TwoSided {
     std::vector<std::vector<int32_t>> tables;   // the host copies of the translation tables, alive until the uploads have completed
 };
 TwoSided concat_two_sided(qe_ctx *ctx, PoolScratch &sc, const qe_result *left, int64_t loff, const qe_result *right, int64_t roff);
+
+// ---- qe_two_sided.cpp: what the two-sided joins share (the hash probe, the ASOF join, the range join) ----------------------
+// What every join of two results is called with.  `who` is the entry point's name: every message begins with it.
+struct TwoSidedCall {
+    const char *who;
+    const qe_result *left, *right;
+    const int32_t *left_by, *right_by;
+    int32_t nby;
+    const int32_t *left_out, *right_out;
+    int32_t nleft_out, nright_out, join_type;
+};
+constexpr uint32_t kJoinsPairs = 1u << QE_JOIN_INNER | 1u << QE_JOIN_LEFT, kJoinsAll = kJoinsPairs | 1u << QE_JOIN_SEMI | 1u << QE_JOIN_ANTI;
+// What can be said without reading either side (a caller's handle is only touched once this has returned): 0 to 7 by columns
+// with both lists there, option_error (the caller's verdict on its own flags, null: none), join_type among join_types (a
+// kJoins.. set), the out lists, "no output column", "a SEMI / ANTI join has no right columns".  All QE_ERR_INVALID_ARG.
+void check_call(const TwoSidedCall &q, uint32_t join_types, const char *option_error);
+// every cols[i] is below ncols, or who + ": <what> column <c> out of range"
+void check_columns(const char *who, const char *what, const int32_t *cols, int32_t n, size_t ncols);
+// a value column of a join: the side it belongs to, its index there and its name in messages ("left lo", "right on")
+struct ValueColumn {
+    bool right;
+    int32_t col;
+    const char *name;
+};
+// What the sides themselves say: every by, value and out column is in range, the by columns agree in type pairwise and the
+// STRING ones have dictionaries, the value columns are DOUBLE, INT64 or INT32 and of one type (all QE_ERR_INVALID_ARG); then
+// the rows of both sides together are at most kMaxRows (QE_ERR_UNSUPPORTED).  The caller's need_device comes after it.
+void check_sides(const TwoSidedCall &q, const ValueColumn *values, int nvalues);
+
+// The key sort of two sides: the by columns and one value column of each side as one result (concat_two_sided; among equal
+// keys the right rows stand first when right_first) and its rows sorted by (by.., value) (SortedRuns); then, by mark(), the
+// sorted rows with a whole key (`eligible`) and the right rows among those (`right`) as bitmaps (launch_asof_eligible), and
+// the ranks of `right` per word.  Queued on the context's stream.  LIFETIME: the key result and `sc` go back to the pool only
+// after the stream has been synchronised -- the caller synchronises before this object or `sc` goes out of scope.
+struct TwoSidedKeys {
+    int64_t nl, nr, n;
+    TwoSided both;                              // both.cat: the key result (its validity pointers are what the kernels read)
+    const qe_sort_key keys[8] = {{0, 0}, {1, 0}, {2, 0}, {3, 0}, {4, 0}, {5, 0}, {6, 0}, {7, 0}};   // ascending; the first nby + 1
+    SortedRuns runs;
+    AsofSides sides;
+    unsigned long long *eligible, *right;       // bitmap_bytes(n) each
+    uint32_t *sums, *right_prefix;              // scan_blocks(words + 1) words of scan scratch, free again; words + 1 ranks
+    TwoSidedKeys(qe_ctx *ctx, PoolScratch &sc, const TwoSidedCall &q, int32_t left_value, int32_t right_value, bool right_first);
+    void mark();   // (its own step: the ASOF join flags its partitions between the sort and this, as it always has)
+};
+
+// what the row gather reads of a source column, whichever kind of column it is
+struct SourceColumn {
+    int type;
+    const void *data;
+    const uint64_t *validity;
+    std::shared_ptr<DictData> dict;
+    bool nullable;
+    SourceColumn(int type, const void *data, const uint64_t *validity, std::shared_ptr<DictData> dict, bool nullable)
+        : type(type), data(data), validity(validity), dict(std::move(dict)), nullable(nullable) {}
+    SourceColumn(const OutColumn &c) : SourceColumn(c.type, c.data, c.validity, c.dict, is_nullable(c)) {}
+};
+// one more column of res: src gathered by rows[0..nout) (gather_column: max_blocks); no launch for nout == 0
+void emit_column(qe_ctx *ctx, qe_result *res, int64_t nout, const SourceColumn &src, const uint32_t *rows, bool force_nullable, int max_blocks);
+// The output step of a join: the listed left columns by lrows, then the listed right columns by rrows (nullable whatever
+// the source when right_nullable: the LEFT join's unmatched rows), into a result of nout rows.
+template <typename L, typename R>
+void emit_joined(qe_ctx *ctx, qe_result *res, int64_t nout, const std::vector<L> &lcols, const int32_t *left_out, int32_t nleft_out,
+                 const uint32_t *lrows, const std::vector<R> &rcols, const int32_t *right_out, int32_t nright_out, const uint32_t *rrows,
+                 bool right_nullable, int max_blocks) {
+    res->cols.reserve((size_t)(nleft_out + nright_out));
+    for (int32_t i = 0; i < nleft_out; i++) emit_column(ctx, res, nout, lcols[(size_t)left_out[i]], lrows, false, max_blocks);
+    for (int32_t i = 0; i < nright_out; i++) emit_column(ctx, res, nout, rcols[(size_t)right_out[i]], rrows, right_nullable, max_blocks);
+}
 
 // ---- qe_api.cpp: plans and launches -------------------------------------------------------------------------
 // What get_plan is asked for; a call site names only what it sets.

@@ -5,7 +5,6 @@
 #include <functional>
 
 #include "qe_exec.h"
-#include "qe_kernels.h"
 #include "qe_scan.h"
 
 namespace qe {
@@ -14,13 +13,8 @@ namespace {
 constexpr int64_t kMaxSideRows = (1ll << 32) - 2;   // rows are uint32 with one sentinel
 constexpr int kMaxDirBits = 26;                     // 64 Mi buckets: the directory stays at 256 MiB
 
-// one side of a join, whichever of the two it is: columns and a row count
-struct SideCol {
-    int type = 0;
-    const void *data = nullptr;
-    const uint64_t *validity = nullptr;
-    std::shared_ptr<DictData> dict;
-};
+// one side of a join, whichever of the two it is: columns (nullable: those with a bitmap) and a row count
+using SideCol = SourceColumn;
 struct Side {
     int64_t nrows = 0;
     std::vector<SideCol> cols;
@@ -32,11 +26,11 @@ Side side_of(const qe_join_input *in, const char *who) {
     Side s;
     if (in->result) {
         s.nrows = in->result->count;
-        for (const OutColumn &c : in->result->cols) s.cols.push_back({c.type, c.data, c.validity, c.dict});
+        for (const OutColumn &c : in->result->cols) s.cols.push_back({c.type, c.data, c.validity, c.dict, c.validity != nullptr});
     } else {
         if (in->batch->schema_only) fail(QE_ERR_INVALID_ARG, std::string(who) + ": a schema-only batch has no rows to join");
         s.nrows = in->batch->nrows;
-        for (const Column &c : in->batch->cols) s.cols.push_back({c.type, c.data, c.validity, c.dict});
+        for (const Column &c : in->batch->cols) s.cols.push_back({c.type, c.data, c.validity, c.dict, c.validity != nullptr});
     }
     for (const SideCol &c : s.cols)
         if (c.type == QE_STRING && !c.dict) fail(QE_ERR_INVALID_ARG, std::string(who) + ": STRING column without dictionary");
@@ -45,8 +39,7 @@ Side side_of(const qe_join_input *in, const char *who) {
 
 void check_cols(const Side &s, const int32_t *cols, int32_t n, const char *who, const char *what) {
     if (n < 0 || (n > 0 && !cols)) fail(QE_ERR_INVALID_ARG, std::string(who) + ": bad " + what + " list");
-    for (int32_t i = 0; i < n; i++)
-        if (cols[i] < 0 || cols[i] >= (int32_t)s.cols.size()) fail(QE_ERR_INVALID_ARG, std::string(who) + ": " + what + " column out of range");
+    check_columns(who, what, cols, n, s.cols.size());
 }
 
 uint64_t hash_mask_from_env() {
@@ -227,12 +220,8 @@ qe_result *probe_table(qe_ctx *ctx, const qe_join_table *t, const qe_join_input 
     if (pairs) pa.brow_out = (uint32_t *)sc.alloc((size_t)total * 4);
     launch_join_write(ctx->stream, pa);
 
-    auto emit = [&](const SideCol &src, const uint32_t *rows, bool force_nullable) {
-        OutColumn &oc = add_column(ctx, res.get(), src.type, force_nullable || src.validity != nullptr, src.dict, total);
-        gather_column(ctx, src.type, src.data, src.validity, rows, total, oc, kGatherBlocksWide);
-    };
-    for (int32_t i = 0; i < nprobe_out; i++) emit(side.cols[(size_t)probe_out[i]], pa.prow_out, false);
-    for (int32_t i = 0; i < nbuild_out; i++) emit(t->build.cols[(size_t)build_out[i]], pa.brow_out, join_type == QE_JOIN_LEFT);
+    emit_joined(ctx, res.get(), total, side.cols, probe_out, nprobe_out, pa.prow_out, t->build.cols, build_out, nbuild_out, pa.brow_out,
+                join_type == QE_JOIN_LEFT, kGatherBlocksWide);   // (no launch for no rows: launch_gather_rows returns at once, as before)
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));
     ctx->join_stats.store(t->m, n, total, (int64_t)(uint32_t)h_ctl[1]);

@@ -1,88 +1,29 @@
 // qe_range.cpp -- host side of the range join of two results (kernels: qe_range.hip): for every left row ALL
 // right rows of the same by tuple whose `on` value lies between the left row's two bounds.  The key columns of the two sides
-// are concatenated (concat_two_sided, qe_exec.h) and sorted by (by.., value) (SortedRuns, qe_exec.h) twice, once with the
-// lower and once with the upper bound as the left rows' value; in each sort a left row reads off how many eligible right rows
-// stand before it.  Both numbers index one list of the eligible right rows, so their difference is the row's match count; a
-// 64-bit scan of the counts and a load-balanced expansion turn them into row pairs for the row gather every operator uses.
-#include <algorithm>
-
+// are sorted as one by (by.., value) (TwoSidedKeys, qe_exec.h) twice, once with the lower and once with the upper bound as the
+// left rows' value; in each sort a left row reads off how many eligible right rows stand before it.  Both numbers index one
+// list of the eligible right rows, so their difference is the row's match count; a 64-bit scan of the counts and a
+// load-balanced expansion turn them into row pairs for the output step of every join (emit_joined).
 #include "qe_exec.h"
-#include "qe_kernels.h"
 #include "qe_scan.h"
 
 namespace qe {
 namespace {
 
-constexpr int kMaxBy = 7;   // with the value column: the sort's 8 keys
-
-struct RangeCall {
-    const qe_result *left, *right;
-    const int32_t *left_by, *right_by;
-    int32_t nby, left_lo, left_hi, right_on, lo_strict, hi_strict, join_type;
-    const int32_t *left_out;
-    int32_t nleft_out;
-    const int32_t *right_out;
-    int32_t nright_out;
-};
-
-// what can be said without reading either result (a caller's handle is only touched once these hold)
-void check_scalars(const RangeCall &q, const char *who) {
-    if (q.nby < 0 || q.nby > kMaxBy) fail(QE_ERR_INVALID_ARG, std::string(who) + ": 0 to 7 by columns");
-    if (q.nby > 0 && (!q.left_by || !q.right_by)) fail(QE_ERR_INVALID_ARG, std::string(who) + ": by columns missing");
-    if ((q.lo_strict != 0 && q.lo_strict != 1) || (q.hi_strict != 0 && q.hi_strict != 1))
-        fail(QE_ERR_INVALID_ARG, std::string(who) + ": a strict flag is 0 or 1");
-    if (q.join_type < QE_JOIN_INNER || q.join_type > QE_JOIN_ANTI) fail(QE_ERR_INVALID_ARG, std::string(who) + ": unknown join type");
-    if (q.nleft_out < 0 || q.nright_out < 0) fail(QE_ERR_INVALID_ARG, std::string(who) + ": negative column count");
-    if ((q.nleft_out > 0 && !q.left_out) || (q.nright_out > 0 && !q.right_out)) fail(QE_ERR_INVALID_ARG, std::string(who) + ": output columns missing");
-    if ((int64_t)q.nleft_out + q.nright_out < 1) fail(QE_ERR_INVALID_ARG, std::string(who) + ": no output column");
-    if ((q.join_type == QE_JOIN_SEMI || q.join_type == QE_JOIN_ANTI) && q.nright_out != 0)
-        fail(QE_ERR_INVALID_ARG, std::string(who) + ": a SEMI / ANTI join has no right columns");
-}
-
-void check_cols(const qe_result *side, const int32_t *cols, int32_t n, const char *who, const char *what) {
-    for (int32_t i = 0; i < n; i++)
-        if (cols[i] < 0 || cols[i] >= (int32_t)side->cols.size())
-            fail(QE_ERR_INVALID_ARG, std::string(who) + ": " + what + " column " + std::to_string(cols[i]) + " out of range");
-}
-
 // One of the two sorts: ord[l] = the eligible right rows that stand before left row l in the order (by.., value), where the
 // left rows' value is column `left_value` and, among equal keys, the right rows stand first when right_first; 0xFFFFFFFF for a
 // left row without a whole key.  rlist (may be null): the eligible right rows in that order.  Everything this needs besides
 // the two outputs is released before it returns.
-void sorted_ordinals(qe_ctx *ctx, const RangeCall &q, int32_t left_value, bool right_first, uint32_t *ord, uint32_t *rlist) {
-    const int32_t nkeys = q.nby + 1;
-    std::vector<int32_t> lkeys(q.left_by, q.left_by + q.nby), rkeys(q.right_by, q.right_by + q.nby);
-    lkeys.push_back(left_value);
-    rkeys.push_back(q.right_on);
-    const int64_t nl = q.left->count, nr = q.right->count, n = nl + nr;
+void sorted_ordinals(qe_ctx *ctx, const TwoSidedCall &q, int32_t left_value, int32_t right_on, bool right_first, uint32_t *ord, uint32_t *rlist) {
     PoolScratch sc(ctx);
-    // the scratch key result, the dictionaries of its STRING by columns settled: the same merge in both sorts
-    const qe_result lview = column_view(q.left, lkeys.data(), nkeys), rview = column_view(q.right, rkeys.data(), nkeys);
-    TwoSided both = concat_two_sided(ctx, sc, &lview, right_first ? nr : 0, &rview, right_first ? 0 : nl);
-    const qe_result *cat = both.cat.get();
-    std::vector<qe_sort_key> keys;
-    for (int32_t k = 0; k < nkeys; k++) keys.push_back({k, 0});
-    SortedRuns runs(ctx, sc, cat, keys.data(), nkeys);
-
-    const int64_t nwords = bitmap_words(n);
-    unsigned long long *eligible = (unsigned long long *)sc.alloc(bitmap_bytes(n));
-    unsigned long long *rbits = (unsigned long long *)sc.alloc(bitmap_bytes(n));
-    uint32_t *sums = (uint32_t *)sc.alloc((size_t)scan_blocks(nwords + 1) * 4);
-    uint32_t *right_prefix = (uint32_t *)sc.alloc((size_t)(nwords + 1) * 4);
-    AsofEligibleArgs ea{};
-    ea.s = AsofSides{runs.rows, n, right_first ? nr : nl, right_first ? 1 : 0};
-    ea.nkeys = nkeys;
-    for (int32_t k = 0; k < nkeys; k++) ea.validity[k] = (const unsigned long long *)cat->cols[(size_t)k].validity;
-    ea.eligible = eligible;
-    ea.right = rbits;
-    launch_asof_eligible(ctx->stream, ea);
-    bitmap_ranks(ctx->stream, (const uint64_t *)rbits, nullptr, n, right_prefix, sums, nullptr);
+    TwoSidedKeys keys(ctx, sc, q, left_value, right_on, right_first);
+    keys.mark();
     RangeOrdinalArgs oa{};
-    oa.s = ea.s;
-    oa.nleft = nl;
-    oa.eligible = eligible;
-    oa.right = rbits;
-    oa.right_prefix = right_prefix;
+    oa.s = keys.sides;
+    oa.nleft = keys.nl;
+    oa.eligible = keys.eligible;
+    oa.right = keys.right;
+    oa.right_prefix = keys.right_prefix;
     oa.ord = ord;
     oa.rlist = rlist;
     launch_range_ordinals(ctx->stream, oa);
@@ -90,34 +31,12 @@ void sorted_ordinals(qe_ctx *ctx, const RangeCall &q, int32_t left_value, bool r
     QE_HIP(hipStreamSynchronize(ctx->stream));   // the key result and this sort's scratch go back to the pool now
 }
 
-qe_result *run_range(qe_ctx *ctx, const RangeCall &q) {
-    const char *who = "qe_result_range_join";
-    check_scalars(q, who);
-    const qe_result *left = q.left, *right = q.right;
-    check_cols(left, q.left_by, q.nby, who, "left by");
-    check_cols(right, q.right_by, q.nby, who, "right by");
-    check_cols(left, &q.left_lo, 1, who, "left lo");
-    check_cols(left, &q.left_hi, 1, who, "left hi");
-    check_cols(right, &q.right_on, 1, who, "right on");
-    check_cols(left, q.left_out, q.nleft_out, who, "left output");
-    check_cols(right, q.right_out, q.nright_out, who, "right output");
-    for (int32_t k = 0; k < q.nby; k++) {
-        const OutColumn &l = left->cols[(size_t)q.left_by[k]], &r = right->cols[(size_t)q.right_by[k]];
-        if (l.type != r.type)
-            fail(QE_ERR_INVALID_ARG, std::string(who) + ": by column " + std::to_string(k) + " is " + type_name(l.type) + " on the left and " +
-                                         type_name(r.type) + " on the right");
-        if (l.type == QE_STRING && (!l.dict || !r.dict)) fail(QE_ERR_INVALID_ARG, std::string(who) + ": STRING by column without dictionary");
-    }
-    const int lo_type = left->cols[(size_t)q.left_lo].type, hi_type = left->cols[(size_t)q.left_hi].type, on_type = right->cols[(size_t)q.right_on].type;
-    for (int t : {lo_type, hi_type, on_type})
-        if (t != QE_DOUBLE && t != QE_INT64 && t != QE_INT32)
-            fail(QE_ERR_INVALID_ARG, std::string(who) + ": a value column is " + type_name(t) + ", not DOUBLE, INT64 or INT32");
-    if (lo_type != on_type || hi_type != on_type)
-        fail(QE_ERR_INVALID_ARG, std::string(who) + ": the value columns are " + type_name(lo_type) + " (lo), " + type_name(hi_type) + " (hi) and " +
-                                     type_name(on_type) + " (on)");
-    const int64_t nl = left->count, nr = right->count;
-    if (nl + nr > kMaxRows) fail(QE_ERR_UNSUPPORTED, std::string(who) + ": 2^32 - 1 rows or more");
+qe_result *run_range(qe_ctx *ctx, const TwoSidedCall &q, int32_t left_lo, int32_t left_hi, int32_t right_on, int32_t lo_strict, int32_t hi_strict) {
+    check_call(q, kJoinsAll, (lo_strict != 0 && lo_strict != 1) || (hi_strict != 0 && hi_strict != 1) ? "a strict flag is 0 or 1" : nullptr);
+    const ValueColumn values[3] = {{false, left_lo, "left lo"}, {false, left_hi, "left hi"}, {true, right_on, "right on"}};
+    check_sides(q, values, 3);
     need_device(ctx);
+    const int64_t nl = q.left->count, nr = q.right->count;
     const bool pairs = q.join_type == QE_JOIN_INNER || q.join_type == QE_JOIN_LEFT, left_join = q.join_type == QE_JOIN_LEFT;
 
     PoolScratch sc(ctx);
@@ -133,8 +52,8 @@ qe_result *run_range(qe_ctx *ctx, const RangeCall &q) {
         uint32_t *ord_hi = (uint32_t *)sc.alloc((size_t)nl * 4);
         if (nr > 0) {
             if (pairs) rlist = (uint32_t *)sc.alloc((size_t)nr * 4);
-            sorted_ordinals(ctx, q, q.left_lo, q.lo_strict != 0, ord_lo, rlist);
-            sorted_ordinals(ctx, q, q.left_hi, q.hi_strict == 0, ord_hi, nullptr);
+            sorted_ordinals(ctx, q, left_lo, right_on, lo_strict != 0, ord_lo, rlist);
+            sorted_ordinals(ctx, q, left_hi, right_on, hi_strict == 0, ord_hi, nullptr);
         } else {   // nothing to match: no sort
             QE_HIP(hipMemsetAsync(ord_lo, 0xFF, (size_t)nl * 4, ctx->stream));
             QE_HIP(hipMemsetAsync(ord_hi, 0xFF, (size_t)nl * 4, ctx->stream));
@@ -176,13 +95,12 @@ qe_result *run_range(qe_ctx *ctx, const RangeCall &q) {
         longest = (int64_t)(uint32_t)h_ctl[1];
         nemit = left_join ? nl : pairs ? (int64_t)h_ctl[2] : nout;
         if (nout < 0 || nemit < 0 || nemit > nl || longest > nr || (nout > 0 && nemit == 0) || (!pairs && nout > nl))
-            fail(QE_ERR_INTERNAL, std::string(who) + ": " + std::to_string(nout) + " output rows from " + std::to_string(nemit) + " of " +
+            fail(QE_ERR_INTERNAL, std::string(q.who) + ": " + std::to_string(nout) + " output rows from " + std::to_string(nemit) + " of " +
                                       std::to_string(nl) + " left rows, longest " + std::to_string(longest));
     }
 
     // ---- 3. the row lists: the kept left rows (SEMI / ANTI), or the expansion into pairs (INNER / LEFT) ----
     ResultPtr res = new_result(ctx, nout);
-    res->cols.reserve((size_t)(q.nleft_out + q.nright_out));
     uint32_t *lrows = nullptr, *rrows = nullptr;
     if (nout > 0) {
         lrows = (uint32_t *)sc.alloc((size_t)nout * 4);
@@ -214,12 +132,8 @@ qe_result *run_range(qe_ctx *ctx, const RangeCall &q) {
     }
 
     // ---- 4. the output: the listed left columns by the left rows, the listed right columns by their matches ----
-    auto emit = [&](const OutColumn &src, const uint32_t *rows, bool force_nullable) {
-        OutColumn &oc = add_column(ctx, res.get(), src.type, force_nullable || is_nullable(src), src.dict, nout);
-        if (nout > 0) gather_column(ctx, src.type, src.data, src.validity, rows, nout, oc, kGatherBlocksWide);
-    };
-    for (int32_t i = 0; i < q.nleft_out; i++) emit(left->cols[(size_t)q.left_out[i]], lrows, false);
-    for (int32_t i = 0; i < q.nright_out; i++) emit(right->cols[(size_t)q.right_out[i]], rrows, left_join);
+    emit_joined(ctx, res.get(), nout, q.left->cols, q.left_out, q.nleft_out, lrows, q.right->cols, q.right_out, q.nright_out, rrows, left_join,
+                kGatherBlocksWide);
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));   // the scratch goes back to the pool now
     ctx->range_stats.store(nl, nr, nout, longest);
@@ -239,9 +153,8 @@ int32_t qe_result_range_join(qe_ctx *ctx, const qe_result *left, const qe_result
                              qe_result **out) {
     if (out) *out = nullptr;
     if (!ctx || !left || !right || !out) return QE_ERR_INVALID_ARG;
-    const RangeCall q{left, right, left_by, right_by, nby, left_lo, left_hi, right_on, lo_strict, hi_strict, join_type,
-                      left_out, nleft_out, right_out, nright_out};
-    return guarded(ctx, [&] { *out = run_range(ctx, q); });
+    const TwoSidedCall q{"qe_result_range_join", left, right, left_by, right_by, nby, left_out, right_out, nleft_out, nright_out, join_type};
+    return guarded(ctx, [&] { *out = run_range(ctx, q, left_lo, left_hi, right_on, lo_strict, hi_strict); });
 }
 
 int32_t qe_ctx_last_range_stats(const qe_ctx *ctx, int64_t out[4]) { return last_stats(ctx, &qe_ctx::range_stats, out); }

@@ -184,13 +184,18 @@ class Context:
                                                                -1 if limit is None else int(limit), C.byref(h)))
         return Result(self, h)
 
+    def _last_stats(self, call, names: Optional[Sequence[str]] = None):
+        """The four stats words a qe_ctx_last_*_stats call reports: as a list, or under `names`."""
+        out = (C.c_int64 * 4)()
+        N.check(self.handle, call(self.handle, out))
+        words = [int(v) for v in out]
+        return words if names is None else dict(zip(names, words))
+
     def last_sort_stats(self) -> dict:
         """qe_ctx_last_sort_stats: what the last order_by / order_by_keys did -- path ("sort" or "select"), rows that went
         into the sort, radix passes and selection passes run."""
-        out = (C.c_int64 * 4)()
-        N.check(self.handle, self._lib.qe_ctx_last_sort_stats(self.handle, out))
-        return {"path": "select" if out[0] == 1 else "sort", "sorted_rows": int(out[1]), "radix_passes": int(out[2]),
-                "select_passes": int(out[3])}
+        words = self._last_stats(self._lib.qe_ctx_last_sort_stats)
+        return {"path": "select" if words[0] == 1 else "sort", "sorted_rows": words[1], "radix_passes": words[2], "select_passes": words[3]}
 
     def join_build(self, side, key_cols: Sequence[int]) -> "JoinTable":
         """qe_join_build: the hash table of an equi-join over the key columns of `side` (a Result or a DeviceBatch)."""
@@ -199,9 +204,7 @@ class Context:
     def last_join_stats(self) -> List[int]:
         """qe_ctx_last_join_stats: [build rows in the table, probe rows, output rows, longest candidate run one probe row
         scanned] of the last join_build / probe on this context."""
-        out = (C.c_int64 * 4)()
-        N.check(self.handle, self._lib.qe_ctx_last_join_stats(self.handle, out))
-        return [int(v) for v in out]
+        return self._last_stats(self._lib.qe_ctx_last_join_stats)
 
     def window(self, result: "Result", partition_by: Sequence[int], order_by: Sequence, functions: Sequence) -> "Result":
         """qe_result_window / qe_result_window_frames: every row of `result`, sorted stably by `partition_by` (columns,
@@ -229,9 +232,7 @@ class Context:
 
     def last_window_stats(self) -> dict:
         """qe_ctx_last_window_stats: rows, partitions, scan tiles and trips of the tile-aggregate scan of the last window()."""
-        out = (C.c_int64 * 4)()
-        N.check(self.handle, self._lib.qe_ctx_last_window_stats(self.handle, out))
-        return {"rows": int(out[0]), "partitions": int(out[1]), "tiles": int(out[2]), "trips": int(out[3])}
+        return self._last_stats(self._lib.qe_ctx_last_window_stats, ("rows", "partitions", "tiles", "trips"))
 
     def group_ordered(self, result: "Result", group_by: Sequence[int], functions: Sequence) -> "Result":
         """qe_result_group_ordered: one row per group of `result`, the groups ascending by the `group_by` columns under the
@@ -248,9 +249,7 @@ class Context:
 
     def last_ordered_stats(self) -> dict:
         """qe_ctx_last_ordered_stats: input rows, groups, sorts run and radix passes of those sorts of the last group_ordered()."""
-        out = (C.c_int64 * 4)()
-        N.check(self.handle, self._lib.qe_ctx_last_ordered_stats(self.handle, out))
-        return {"rows": int(out[0]), "groups": int(out[1]), "sorts": int(out[2]), "radix_passes": int(out[3])}
+        return self._last_stats(self._lib.qe_ctx_last_ordered_stats, ("rows", "groups", "sorts", "radix_passes"))
 
     def set_op(self, left: "Result", right: "Result", op: int, all: bool = False) -> "Result":
         """qe_result_set_op: UNION / INTERSECT / EXCEPT (native.SET_*) of two results of one schema, with `all` the multiset
@@ -264,9 +263,7 @@ class Context:
     def last_set_stats(self) -> dict:
         """qe_ctx_last_set_stats: left rows, right rows, distinct tuples the sort found (0 for UNION ALL) and STRING columns
         whose right-side codes were translated, of the last set_op()."""
-        out = (C.c_int64 * 4)()
-        N.check(self.handle, self._lib.qe_ctx_last_set_stats(self.handle, out))
-        return {"left_rows": int(out[0]), "right_rows": int(out[1]), "tuples": int(out[2]), "translated_columns": int(out[3])}
+        return self._last_stats(self._lib.qe_ctx_last_set_stats, ("left_rows", "right_rows", "tuples", "translated_columns"))
 
     def asof_join(self, left: "Result", right: "Result", left_by: Sequence[int], right_by: Sequence[int], left_on: int, right_on: int,
                   direction: int = N.ASOF_BACKWARD, strict: bool = False, join_type: int = N.JOIN_LEFT,
@@ -285,9 +282,7 @@ class Context:
     def last_asof_stats(self) -> dict:
         """qe_ctx_last_asof_stats: left rows, right rows, left rows that found a match and by partitions the sort found over
         both sides together, of the last asof_join()."""
-        out = (C.c_int64 * 4)()
-        N.check(self.handle, self._lib.qe_ctx_last_asof_stats(self.handle, out))
-        return {"left_rows": int(out[0]), "right_rows": int(out[1]), "matched": int(out[2]), "partitions": int(out[3])}
+        return self._last_stats(self._lib.qe_ctx_last_asof_stats, ("left_rows", "right_rows", "matched", "partitions"))
 
     def range_join(self, left: "Result", right: "Result", left_by: Sequence[int], right_by: Sequence[int], left_lo: int, left_hi: int,
                    right_on: int, lo_strict: bool = False, hi_strict: bool = False, join_type: int = N.JOIN_INNER,
@@ -308,9 +303,7 @@ class Context:
     def last_range_stats(self) -> dict:
         """qe_ctx_last_range_stats: left rows, right rows, output rows and the most matches any one left row has, of the last
         range_join()."""
-        out = (C.c_int64 * 4)()
-        N.check(self.handle, self._lib.qe_ctx_last_range_stats(self.handle, out))
-        return {"left_rows": int(out[0]), "right_rows": int(out[1]), "output_rows": int(out[2]), "longest": int(out[3])}
+        return self._last_stats(self._lib.qe_ctx_last_range_stats, ("left_rows", "right_rows", "output_rows", "longest"))
 
     def concat(self, parts: Sequence["Result"]) -> "Result":
         """qe_result_concat: results of this device, concatenated in the given order."""

@@ -226,7 +226,88 @@ def _join_key(values: Sequence[Any]):
     return tuple(key)
 
 
-class HashJoinOperator(DeviceResultOperator):
+class _TwoSidedJoinOperator(DeviceResultOperator):
+    """What the joins of two sources share: the checks of the key and output lists and of the join type, the draining of the
+    two sources (once when they are one object), the width of the NULL tail of a LEFT join, and the loop that turns "the right
+    rows this left row matches" (``_matches``, over what ``_index`` made of the right rows) into INNER / LEFT / SEMI / ANTI rows:
+    left-row order, the matches of one row in the order ``_matches`` gives them, an unmatched LEFT row in its place with every
+    right column ``None``.  A subclass names its public attributes: ``<side>``, ``<side>_<key word>`` and ``<side>_out``."""
+
+    _sides = ("left", "right")
+    _key_word = "by"
+    _key_counts = (0, 7)
+    _join_types: Sequence[int] = (N.JOIN_INNER, N.JOIN_LEFT, N.JOIN_SEMI, N.JOIN_ANTI)
+
+    def __init__(self, left: Operator, right: Operator, left_by: Sequence[int], right_by: Sequence[int], join_type: int,
+                 left_out: Optional[Sequence[int]], right_out: Optional[Sequence[int]]):
+        name, (lname, rname), (fewest, most) = type(self).__name__, self._sides, self._key_counts
+        if left is None or right is None:
+            raise ValueError(f"{name}: two sources")
+        self._by = [int(c) for c in left_by], [int(c) for c in right_by]
+        if not fewest <= len(self._by[0]) <= most or len(self._by[0]) != len(self._by[1]):
+            raise ValueError(f"{name}: {fewest} to {most} {self._key_word} columns, as many on the {lname} side as on the {rname} side")
+        if isinstance(join_type, bool) or join_type not in self._join_types:
+            raise ValueError(f"{name}: " + ("unknown join type" if len(self._join_types) == 4 else "the join type is INNER or LEFT"))
+        self.join_type = int(join_type)
+        self._pairs = self.join_type in (N.JOIN_INNER, N.JOIN_LEFT)
+        if not self._pairs and right_out:
+            raise ValueError(f"{name}: a SEMI / ANTI join has no {rname} columns")
+        self._out = [None if out is None else [int(c) for c in out] for out in (left_out, right_out)]
+        no_right_column = not self._pairs or (self._out[1] is not None and not self._out[1])
+        if self._out[0] is not None and not self._out[0] and no_right_column:
+            raise ValueError(f"{name}: no output column")
+        for side, source, by, out in zip(self._sides, (left, right), self._by, self._out):
+            setattr(self, side, source)
+            setattr(self, f"{side}_{self._key_word}", by)
+            setattr(self, f"{side}_out", out)
+        self._set_sources(left, right)
+
+    def _out_lists(self, lres: E.Result, rres: E.Result):
+        """The output lists of the device call: a list that was not given is every column of its side (SEMI / ANTI: no right one)."""
+        left_out, right_out = self._out
+        return (list(range(lres.ncols)) if left_out is None else left_out,
+                (list(range(rres.ncols)) if self._pairs else []) if right_out is None else right_out)
+
+    def _index(self, right_rows: List[List[Any]]):
+        return right_rows
+
+    def _matches(self, row: List[Any], index) -> List[List[Any]]:
+        raise NotImplementedError
+
+    def _rows_host(self) -> List[List[Any]]:
+        left, right = self._sources
+        left_rows = mapTo(left, [], lambda row: list(row))
+        right_rows = left_rows if right is left else mapTo(right, [], lambda row: list(row))
+        left_out, right_out = self._out
+        if right_out is None:
+            if not self._pairs:
+                right_out = []
+            elif right_rows:
+                right_out = list(range(len(right_rows[0])))
+            elif self.join_type == N.JOIN_LEFT and left_rows:
+                rname = self._sides[1]
+                raise ValueError(f"{type(self).__name__}: {rname}_out must be given when a LEFT join's {rname} source yields no row")
+            else:
+                right_out = []
+        index = self._index(right_rows)
+        out = []
+        for row in left_rows:
+            head = [row[c] for c in (range(len(row)) if left_out is None else left_out)]
+            matches = self._matches(row, index)
+            if self.join_type == N.JOIN_SEMI:
+                if matches:
+                    out.append(head)
+            elif self.join_type == N.JOIN_ANTI:
+                if not matches:
+                    out.append(head)
+            elif matches:
+                out.extend(head + [m[c] for c in right_out] for m in matches)
+            elif self.join_type == N.JOIN_LEFT:
+                out.append(head + [None] * len(right_out))
+        return out
+
+
+class HashJoinOperator(_TwoSidedJoinOperator):
     """Equi-join of a probe source against a build source: ``probe_keys[i]`` pairs with ``build_keys[i]`` (column
     indices).  ``join_type`` is ``native.JOIN_INNER / JOIN_LEFT / JOIN_SEMI / JOIN_ANTI``.  A row is the listed probe
     columns followed by the listed build columns (``None`` = every column of that side; SEMI and ANTI have no build
@@ -239,66 +320,35 @@ class HashJoinOperator(DeviceResultOperator):
     sorts in HBM too.  Any other pair of sources is drained and joined on the host with a dict from the key tuple to the
     list of build rows in order -- the executable statement of the semantics, and the expectation of the device tests."""
 
+    _sides = ("probe", "build")
+    _key_word = "keys"
+    _key_counts = (1, 4)
+
     def __init__(self, probe: Operator, build: Operator, probe_keys: Sequence[int], build_keys: Sequence[int],
                  join_type: int = N.JOIN_INNER, probe_out: Optional[Sequence[int]] = None,
                  build_out: Optional[Sequence[int]] = None):
-        self.probe, self.build = probe, build
-        self.probe_keys, self.build_keys = [int(c) for c in probe_keys], [int(c) for c in build_keys]
-        if not 1 <= len(self.probe_keys) <= 4 or len(self.probe_keys) != len(self.build_keys):
-            raise ValueError("HashJoinOperator: 1 to 4 key columns, as many on the probe side as on the build side")
-        if join_type not in (N.JOIN_INNER, N.JOIN_LEFT, N.JOIN_SEMI, N.JOIN_ANTI):
-            raise ValueError("HashJoinOperator: unknown join type")
-        self.join_type = join_type
-        self._pairs = join_type in (N.JOIN_INNER, N.JOIN_LEFT)
-        if not self._pairs and build_out:
-            raise ValueError("HashJoinOperator: a SEMI / ANTI join has no build columns")
-        self.probe_out = None if probe_out is None else [int(c) for c in probe_out]
-        self.build_out = None if build_out is None else [int(c) for c in build_out]
-        self._set_sources(probe, build)
+        super().__init__(probe, build, probe_keys, build_keys, join_type, probe_out, build_out)
 
     def _device_call(self, pres: E.Result, bres: E.Result) -> E.Result:
-        probe_out = list(range(pres.ncols)) if self.probe_out is None else self.probe_out
-        build_out = (list(range(bres.ncols)) if self._pairs else []) if self.build_out is None else self.build_out
+        probe_out, build_out = self._out_lists(pres, bres)
         table = self.ctx.join_build(bres, self.build_keys)
         try:
             return table.probe(pres, self.probe_keys, self.join_type, probe_out, build_out)
         finally:
             table.free()
 
-    def _rows_host(self) -> List[List[Any]]:
-        build_rows = mapTo(self.build, [], lambda row: list(row))
-        probe_rows = mapTo(self.probe, [], lambda row: list(row))
-        build_out = self.build_out
-        if build_out is None:
-            if not self._pairs:
-                build_out = []
-            elif build_rows:
-                build_out = list(range(len(build_rows[0])))
-            elif self.join_type == N.JOIN_LEFT and probe_rows:
-                raise ValueError("HashJoinOperator: build_out must be given when a LEFT join's build source yields no row")
-            else:
-                build_out = []
+    def _index(self, build_rows: List[List[Any]]) -> dict:
+        """The key tuple -> the build rows that hold it, in build-row order."""
         table: dict = {}
         for row in build_rows:
             key = _join_key([row[c] for c in self.build_keys])
             if key is not None:
                 table.setdefault(key, []).append(row)
-        out = []
-        for row in probe_rows:
-            head = [row[c] for c in (range(len(row)) if self.probe_out is None else self.probe_out)]
-            key = _join_key([row[c] for c in self.probe_keys])
-            matches = table.get(key, []) if key is not None else []
-            if self.join_type == N.JOIN_SEMI:
-                if matches:
-                    out.append(head)
-            elif self.join_type == N.JOIN_ANTI:
-                if not matches:
-                    out.append(head)
-            elif matches:
-                out.extend(head + [m[c] for c in build_out] for m in matches)
-            elif self.join_type == N.JOIN_LEFT:
-                out.append(head + [None] * len(build_out))
-        return out
+        return table
+
+    def _matches(self, row: List[Any], table: dict) -> List[List[Any]]:
+        key = _join_key([row[c] for c in self.probe_keys])
+        return table.get(key, []) if key is not None else []
 
 
 def _window_min(a: float, b: float, want_max: bool) -> float:
@@ -621,7 +671,7 @@ class SetOperator(DeviceResultOperator):
         return out
 
 
-class AsofJoinOperator(DeviceResultOperator):
+class AsofJoinOperator(_TwoSidedJoinOperator):
     """ASOF join: for every left row the ONE right row with an equal by tuple whose ``on`` value is nearest at or before it
     (``direction=native.ASOF_BACKWARD``) or at or after it (``ASOF_FORWARD``) -- for every trade the last quote of its symbol.
     ``left_by[i]`` pairs with ``right_by[i]`` (column indices, 0 to 7 of them; none: the whole input is one partition); by
@@ -641,28 +691,18 @@ class AsofJoinOperator(DeviceResultOperator):
     host by a plain nested loop over ``_join_key`` and ``_compare_key`` -- the executable statement of the semantics, written
     for clarity, and the expectation of the device tests."""
 
+    _join_types = (N.JOIN_INNER, N.JOIN_LEFT)
+
     def __init__(self, left: Operator, right: Operator, left_by: Sequence[int], right_by: Sequence[int], left_on: int, right_on: int,
                  direction: int = N.ASOF_BACKWARD, strict: bool = False, join_type: int = N.JOIN_LEFT,
                  left_out: Optional[Sequence[int]] = None, right_out: Optional[Sequence[int]] = None):
-        if left is None or right is None:
-            raise ValueError("AsofJoinOperator: two sources")
-        self.left, self.right = left, right
-        self.left_by, self.right_by = [int(c) for c in left_by], [int(c) for c in right_by]
-        if len(self.left_by) > 7 or len(self.left_by) != len(self.right_by):
-            raise ValueError("AsofJoinOperator: 0 to 7 by columns, as many on the left as on the right")
+        super().__init__(left, right, left_by, right_by, join_type, left_out, right_out)
         self.left_on, self.right_on = int(left_on), int(right_on)
         if isinstance(direction, bool) or direction not in (N.ASOF_BACKWARD, N.ASOF_FORWARD):
             raise ValueError("AsofJoinOperator: unknown direction")
         if strict not in (False, True, 0, 1):
             raise ValueError("AsofJoinOperator: strict is False or True")
-        if isinstance(join_type, bool) or join_type not in (N.JOIN_INNER, N.JOIN_LEFT):
-            raise ValueError("AsofJoinOperator: the join type is INNER or LEFT")
-        self.direction, self.strict, self.join_type = int(direction), bool(strict), int(join_type)
-        self.left_out = None if left_out is None else [int(c) for c in left_out]
-        self.right_out = None if right_out is None else [int(c) for c in right_out]
-        if self.left_out is not None and self.right_out is not None and not self.left_out + self.right_out:
-            raise ValueError("AsofJoinOperator: no output column")
-        self._set_sources(left, right)
+        self.direction, self.strict = int(direction), bool(strict)
 
     @staticmethod
     def _on_key(value: Any):
@@ -689,35 +729,17 @@ class AsofJoinOperator(DeviceResultOperator):
                 best, best_on = r, r_on
         return best
 
-    def _rows_host(self) -> List[List[Any]]:
-        left_rows = mapTo(self.left, [], lambda row: list(row))
-        right_rows = left_rows if self.right is self.left else mapTo(self.right, [], lambda row: list(row))
-        right_out = self.right_out
-        if right_out is None:
-            if right_rows:
-                right_out = list(range(len(right_rows[0])))
-            elif self.join_type == N.JOIN_LEFT and left_rows:
-                raise ValueError("AsofJoinOperator: right_out must be given when a LEFT join's right source yields no row")
-            else:
-                right_out = []
-        out = []
-        for row in left_rows:
-            head = [row[c] for c in (range(len(row)) if self.left_out is None else self.left_out)]
-            match = self._match(row, right_rows)
-            if match is not None:
-                out.append(head + [match[c] for c in right_out])
-            elif self.join_type == N.JOIN_LEFT:
-                out.append(head + [None] * len(right_out))
-        return out
+    def _matches(self, row: List[Any], right_rows: List[List[Any]]) -> List[List[Any]]:
+        match = self._match(row, right_rows)
+        return [] if match is None else [match]
 
     def _device_call(self, lres: E.Result, rres: E.Result) -> E.Result:
-        left_out = list(range(lres.ncols)) if self.left_out is None else self.left_out
-        right_out = list(range(rres.ncols)) if self.right_out is None else self.right_out
+        left_out, right_out = self._out_lists(lres, rres)
         return self.ctx.asof_join(lres, rres, self.left_by, self.right_by, self.left_on, self.right_on, self.direction, self.strict,
                                   self.join_type, left_out, right_out)
 
 
-class RangeJoinOperator(DeviceResultOperator):
+class RangeJoinOperator(_TwoSidedJoinOperator):
     """Range join: for every left row ALL right rows with an equal by tuple whose ``on`` value lies in the left row's interval
     ``[lo, hi]`` -- all quotes in the five seconds before a trade.  ``left_by[i]`` pairs with ``right_by[i]`` (column indices, 0
     to 7 of them; none: the whole input is one partition); by tuples are equal as hash-join keys are (every NaN one value, -0.0
@@ -740,27 +762,11 @@ class RangeJoinOperator(DeviceResultOperator):
     def __init__(self, left: Operator, right: Operator, left_by: Sequence[int], right_by: Sequence[int], left_lo: int, left_hi: int,
                  right_on: int, lo_strict: bool = False, hi_strict: bool = False, join_type: int = N.JOIN_INNER,
                  left_out: Optional[Sequence[int]] = None, right_out: Optional[Sequence[int]] = None):
-        if left is None or right is None:
-            raise ValueError("RangeJoinOperator: two sources")
-        self.left, self.right = left, right
-        self.left_by, self.right_by = [int(c) for c in left_by], [int(c) for c in right_by]
-        if len(self.left_by) > 7 or len(self.left_by) != len(self.right_by):
-            raise ValueError("RangeJoinOperator: 0 to 7 by columns, as many on the left as on the right")
+        super().__init__(left, right, left_by, right_by, join_type, left_out, right_out)
         self.left_lo, self.left_hi, self.right_on = int(left_lo), int(left_hi), int(right_on)
         if lo_strict not in (False, True, 0, 1) or hi_strict not in (False, True, 0, 1):
             raise ValueError("RangeJoinOperator: a strict flag is False or True")
-        if isinstance(join_type, bool) or join_type not in (N.JOIN_INNER, N.JOIN_LEFT, N.JOIN_SEMI, N.JOIN_ANTI):
-            raise ValueError("RangeJoinOperator: unknown join type")
-        self.lo_strict, self.hi_strict, self.join_type = bool(lo_strict), bool(hi_strict), int(join_type)
-        self._pairs = self.join_type in (N.JOIN_INNER, N.JOIN_LEFT)
-        if not self._pairs and right_out:
-            raise ValueError("RangeJoinOperator: a SEMI / ANTI join has no right columns")
-        self.left_out = None if left_out is None else [int(c) for c in left_out]
-        self.right_out = None if right_out is None else [int(c) for c in right_out]
-        no_right_column = not self._pairs or (self.right_out is not None and not self.right_out)
-        if self.left_out is not None and not self.left_out and no_right_column:
-            raise ValueError("RangeJoinOperator: no output column")
-        self._set_sources(left, right)
+        self.lo_strict, self.hi_strict = bool(lo_strict), bool(hi_strict)
 
     @staticmethod
     def _value_key(value: Any):
@@ -788,38 +794,8 @@ class RangeJoinOperator(DeviceResultOperator):
         found.sort(key=lambda item: item[0])                   # stable: ties stay in right row order
         return [r for _, r in found]
 
-    def _rows_host(self) -> List[List[Any]]:
-        left_rows = mapTo(self.left, [], lambda row: list(row))
-        right_rows = left_rows if self.right is self.left else mapTo(self.right, [], lambda row: list(row))
-        right_out = self.right_out
-        if right_out is None:
-            if not self._pairs:
-                right_out = []
-            elif right_rows:
-                right_out = list(range(len(right_rows[0])))
-            elif self.join_type == N.JOIN_LEFT and left_rows:
-                raise ValueError("RangeJoinOperator: right_out must be given when a LEFT join's right source yields no row")
-            else:
-                right_out = []
-        out = []
-        for row in left_rows:
-            head = [row[c] for c in (range(len(row)) if self.left_out is None else self.left_out)]
-            matches = self._matches(row, right_rows)
-            if self.join_type == N.JOIN_SEMI:
-                if matches:
-                    out.append(head)
-            elif self.join_type == N.JOIN_ANTI:
-                if not matches:
-                    out.append(head)
-            elif matches:
-                out.extend(head + [m[c] for c in right_out] for m in matches)
-            elif self.join_type == N.JOIN_LEFT:
-                out.append(head + [None] * len(right_out))
-        return out
-
     def _device_call(self, lres: E.Result, rres: E.Result) -> E.Result:
-        left_out = list(range(lres.ncols)) if self.left_out is None else self.left_out
-        right_out = (list(range(rres.ncols)) if self._pairs else []) if self.right_out is None else self.right_out
+        left_out, right_out = self._out_lists(lres, rres)
         return self.ctx.range_join(lres, rres, self.left_by, self.right_by, self.left_lo, self.left_hi, self.right_on, self.lo_strict,
                                    self.hi_strict, self.join_type, left_out, right_out)
 

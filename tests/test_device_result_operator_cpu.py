@@ -1,10 +1,10 @@
-"""The protocol that the five operators holding a device result share (``DeviceResultOperator``), without a GPU: stub sources
+"""The protocol that the six operators holding a device result share (``DeviceResultOperator``), without a GPU: stub sources
 that record their calls, and a stub context whose device call returns a stub result or raises."""
 import pytest
 
 from queryengine_amd import native as N
 from queryengine_amd.operators import (AsofJoinOperator, DeviceResultOperator, HashJoinOperator, OrderByOperator,
-                                       OrderedAggregateOperator, SetOperator, WindowOperator)
+                                       OrderedAggregateOperator, RangeJoinOperator, SetOperator, WindowOperator)
 
 
 class StubColumn:
@@ -34,7 +34,7 @@ class StubResult:
 
 
 class StubContext:
-    """Every device call of the five operators: logs itself, then returns a result or raises."""
+    """Every device call of the six operators: logs itself, then returns a result or raises."""
 
     def __init__(self, log, fail=False):
         self.log, self.fail = log, fail
@@ -55,6 +55,9 @@ class StubContext:
         return self._call("call", lres, rres)
 
     def asof_join(self, lres, rres, *args):
+        return self._call("call", lres, rres)
+
+    def range_join(self, lres, rres, *args):
         return self._call("call", lres, rres)
 
     def join_build(self, bres, keys):      # the join: the table is built from the build side and probed with the probe side
@@ -109,6 +112,7 @@ OPERATORS = {
     "ordered": (1, lambda a: OrderedAggregateOperator(a, [0], [(N.OSA_MODE, 1)])),
     "setop": (2, lambda a, b: SetOperator(a, b, N.SET_UNION)),
     "asof": (2, lambda a, b: AsofJoinOperator(a, b, [], [], 1, 1)),
+    "range": (2, lambda a, b: RangeJoinOperator(a, b, [], [], 0, 1, 1)),
 }
 ALL = sorted(OPERATORS)
 TWO_SIDED = [name for name in ALL if OPERATORS[name][0] == 2]

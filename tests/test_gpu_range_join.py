@@ -12,6 +12,7 @@ Not tested: outputs beyond 2^32 rows and left rows + right rows >= 2^32 - 1 (the
 QE_ERR_OOM; QE_ERR_HIP on a planning-only context (it cannot hold a result); a STRING by column without a dictionary, which
 cannot be built through the ABI.  The errors decided from the scalar arguments alone are in tests/test_range_join_cpu.py."""
 import ctypes as C
+import random
 
 import numpy as np
 import pytest
@@ -306,6 +307,42 @@ def test_equality_as_a_range_equals_the_hash_join(gpu_ctx, t):
                 hashed.free()
                 ranged.free()
             pair.check([], [], 0, 0, 0, (False, False, join_type), [1, 0, 2], right_out, "equality")
+    finally:
+        table.free()
+        pair.free()
+
+
+def test_the_joins_agree_on_a_string_by_and_a_double_value(gpu_ctx):
+    """The hash join on (by, value) against the range join with lo == hi == value, both ends inclusive, over one pair of
+    results: the two share their argument checks and their output step, and equality of hash keys is ``Double.compareTo``
+    equality (every NaN one value, -0.0 and 0.0 two).  300 left and 700 right rows: partial last bitmap words on both sides, a
+    by dictionary that is translated, and more than two expansion tiles of INNER output."""
+    rnd = random.Random(7)
+    by_pool, value_pool = [None, "a", "b", "c"], [None, NAN, -0.0, 0.0, 1.5, -2.25, 3.0, INF]
+
+    def side(n, dictionary):
+        rows = [(rnd.choice(by_pool), rnd.choice(value_pool)) for _ in range(n)]
+        by = Column(S, np.array([0 if b is None else dictionary.index(b) for b, _ in rows], dtype=np.int32),
+                    np.array([b is not None for b, _ in rows]), dictionary)
+        value = Column(D, np.array([0.0 if v is None else v for _, v in rows]), np.array([v is not None for _, v in rows]))
+        return [by, value, Column(I64, np.arange(n, dtype=np.int64))]
+
+    pair = Pair(gpu_ctx, side(300, ["a", "b", "c"]), side(700, ["c", "a", "b"]))      # two dictionary objects, two orders
+    table = gpu_ctx.join_build(pair.rres, [0, 1])
+    try:
+        for join_type, rows in zip(JOINS, (4122, 4228, 194, 106)):                    # what the host operators give for these rows
+            right_out = [2, 1, 0] if join_type in (INNER, LEFT) else []
+            hashed = table.probe(pair.lres, [0, 1], join_type, [2, 0, 1], right_out)
+            ranged = gpu_ctx.range_join(pair.lres, pair.rres, [0], [0], 1, 1, 1, False, False, join_type, [2, 0, 1], right_out)
+            try:
+                assert ranged.count == hashed.count == rows, JOIN_NAMES[join_type]
+                assert join_type != INNER or ranged.count > 2 * TILE
+                assert nullable_of(ranged) == nullable_of(hashed)
+                assert [c.dictionary for c in ranged.to_columns()] == [c.dictionary for c in hashed.to_columns()]
+                assert column_bytes(ranged) == column_bytes(hashed), JOIN_NAMES[join_type]         # row for row, bit for bit
+            finally:
+                hashed.free()
+                ranged.free()
     finally:
         table.free()
         pair.free()

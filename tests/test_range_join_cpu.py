@@ -245,8 +245,9 @@ def test_constants_of_the_python_layer():
     assert N.RANGE_EXPAND_TILE == int(re.search(r"constexpr\s+int\s+kRangeExpandTile\s*=\s*(\d+)\s*;", text).group(1))
     kernels = open(os.path.join(ROOT, "queryengine_amd", "csrc", "qe_range.hip")).read()
     assert "dim3(256)" in kernels and "dim3(128)" not in kernels and "dim3(512)" not in kernels     # RANGE_BLOCKS counts blocks of 256 lanes
-    host = open(os.path.join(ROOT, "queryengine_amd", "csrc", "qe_range.cpp")).read()
-    assert "launch_asof_eligible(" in host and "void asof_eligible" not in kernels                  # the eligibility kernel is reused, not copied
+    csrc = os.path.join(ROOT, "queryengine_amd", "csrc")
+    callers = sorted(f for f in os.listdir(csrc) if f.endswith(".cpp") and "launch_asof_eligible(" in open(os.path.join(csrc, f)).read())
+    assert callers == ["qe_two_sided.cpp"] and "void asof_eligible" not in kernels                  # the eligibility kernel is reused, not copied
     header = open(os.path.join(ROOT, "include", "qe_hip.h")).read()
     assert re.search(r"QE_JOIN_INNER\s*=\s*0\s*,\s*QE_JOIN_LEFT\s*=\s*1\s*,\s*QE_JOIN_SEMI\s*=\s*2\s*,\s*QE_JOIN_ANTI\s*=\s*3", header)
 
