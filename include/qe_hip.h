@@ -303,6 +303,20 @@ int32_t qe_filter_groupby_prepare(qe_ctx *ctx, const qe_batch *batch, const qe_e
                                   const qe_expr *const *keys, int32_t nkeys,
                                   const qe_expr *const *exprs, const int32_t *agg_fns, int32_t nagg);
 
+/* what the last qe_filter_groupby of this context did (zeros before the first one): qe_ctx_last_form tells
+ * the three forms apart, this the routes inside them and what the call had to repeat.
+ * out[0] the route that produced the result, QE_GROUPBY_ROUTE_*;
+ * out[1] launches of this call that were abandoned and repeated another way: the error word came back non-zero (3: a global
+ *        or id table more than half full or a probe sequence exhausted, 4: the keys do not fit a workgroup's LDS table,
+ *        6: a hash partition's table filled up) or the skew rule of the hash-partitioned form fired;
+ * out[2] the capacity that sufficed: entries of the global table (HASHED), entries of the id table (DENSE_IDS), buckets per
+ *        partition (HASH_PARTITIONED_*), groups per partition (DENSE_KEY_RANGE), groups of the table (DENSE_LDS, DENSE_GLOBAL);
+ * out[3] partitions of the partitioned passes that ran (DENSE_IDS: of the dense pass over the ids), 0 where none did. */
+enum { QE_GROUPBY_ROUTE_NONE = 0, QE_GROUPBY_ROUTE_DENSE_LDS = 1, QE_GROUPBY_ROUTE_DENSE_KEY_RANGE = 2,
+       QE_GROUPBY_ROUTE_DENSE_GLOBAL = 3, QE_GROUPBY_ROUTE_HASHED = 4, QE_GROUPBY_ROUTE_DENSE_IDS = 5,
+       QE_GROUPBY_ROUTE_HASH_PARTITIONED_HOST = 6, QE_GROUPBY_ROUTE_HASH_PARTITIONED_DEVICE = 7 };
+int32_t qe_ctx_last_groupby_stats(const qe_ctx *ctx, int64_t out[4]);
+
 /* plan-time preparation of the aggregate plan (JIT compile + cache), no execution */
 int32_t qe_filter_aggregate_prepare(qe_ctx *ctx, const qe_batch *batch, const qe_expr *filter,
                                     const qe_expr *const *exprs, const int32_t *agg_fns, int32_t nagg);

@@ -34,6 +34,7 @@ internal object QeNative {
     // ctx, batch, filter|NULL, qe_expr*[nkeys], nkeys, qe_expr*[nagg], int32 fns[nagg], nagg, qe_result** -> status
     val qe_filter_groupby = handle("qe_filter_groupby", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
             JAVA_INT, ADDRESS)
+    val qe_ctx_last_groupby_stats = handle("qe_ctx_last_groupby_stats", JAVA_INT, ADDRESS, ADDRESS)   // ctx, long[4]: route, abandoned launches, capacity, partitions
     val qe_result_count = handle("qe_result_count", JAVA_LONG, ADDRESS)
     val qe_result_ncols = handle("qe_result_ncols", JAVA_INT, ADDRESS)
     val qe_result_column = handle("qe_result_column", JAVA_INT, ADDRESS, JAVA_INT, ADDRESS)

@@ -60,6 +60,15 @@ int stream_grid(qe_ctx *ctx, const Plan &plan, int64_t n, int wgs_per_cu, int64_
     return (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + waves - 1) / waves, (int64_t)device_cus(ctx->device) * wgs_per_cu));
 }
 
+// qe_ctx_last_groupby_stats (qe_hip.h): run_groupby zeroes the words, a launch that is given up counts itself, and the executor
+// that produces the result names its route, the capacity that sufficed and its partitions.
+void stats_abandoned(qe_ctx *ctx) { ctx->groupby_stats.w[1]++; }
+void stats_route(qe_ctx *ctx, int route, int64_t capacity, int64_t partitions) {
+    ctx->groupby_stats.w[0] = route;
+    ctx->groupby_stats.w[2] = capacity;
+    ctx->groupby_stats.w[3] = partitions;
+}
+
 // ---- results built on the host ----------------------------------------------------------------------------------------------
 // Column images that asynchronous uploads read: alive until the caller has synchronised the stream.
 using HostStaging = std::vector<ColumnImage>;
@@ -283,11 +292,16 @@ qe_result *run_groupby_dense(qe_ctx *ctx, const qe_batch *batch, const std::shar
         }
         bracket_close(ctx);
         QE_HIP(hipStreamSynchronize(ctx->stream));   // the temporaries go back to the pool when this scope ends
+        stats_route(ctx, QE_GROUPBY_ROUTE_DENSE_KEY_RANGE, cg.part_groups, pp.P);
     } else if (n > 0) {
         FusedParams p;
         fill_inputs(p, batch, *plan);
         p.agg_partial = (double *)d_tab;
         launch_fused(ctx, *plan, p, stream_grid(ctx, *plan, n, plan->geo.threads >= 1024 ? 1 : 4));   // a 1024-thread workgroup owns its CU (and merges its table once)
+        stats_route(ctx, cg.table_in_lds ? QE_GROUPBY_ROUTE_DENSE_LDS : QE_GROUPBY_ROUTE_DENSE_GLOBAL, G, 0);
+    } else {
+        stats_route(ctx, cg.table_in_lds ? QE_GROUPBY_ROUTE_DENSE_LDS : cg.partitioned && !no_partition ? QE_GROUPBY_ROUTE_DENSE_KEY_RANGE : QE_GROUPBY_ROUTE_DENSE_GLOBAL,
+                    cg.partitioned && !no_partition ? cg.part_groups : G, 0);   // nothing to launch: the route the plan stands for
     }
     QE_HIP(hipMemcpyAsync(tab.data(), d_tab, tab.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     QE_HIP(hipStreamSynchronize(ctx->stream));
@@ -345,6 +359,7 @@ qe_result *run_groupby_ids(qe_ctx *ctx, const qe_batch *batch, const Plan &plan,
         build_ms += bracket_ms(ctx);
         const unsigned int *hc = (const unsigned int *)ctx->h_ctrl;
         if (hc[1] != 0) {   // more than half full: a bigger table, again (the launch stopped at once: an attempt costs little)
+            stats_abandoned(ctx);
             if (many_keys && plan.id_capacity <= 0) {   // the first table of a plan that knows nothing yet: the caller takes over
                 *many_keys = true;
                 return nullptr;
@@ -396,6 +411,7 @@ qe_result *run_groupby_ids(qe_ctx *ctx, const qe_batch *batch, const Plan &plan,
     auto dplan = get_plan(ctx, &tmp, PlanRequest{filter, exprs, nagg, agg_fns, kp, 1});
     if (dplan->cg.hashed) fail(QE_ERR_INTERNAL, "dense-id plan came out hashed");
     const ResultPtr r = own_result(ctx, run_groupby_dense(ctx, &tmp, dplan, agg_fns, nagg));
+    stats_route(ctx, QE_GROUPBY_ROUTE_DENSE_IDS, C, ctx->groupby_stats.w[3]);   // (the partitions are the dense pass's)
     ctx->last_ms += build_ms;   // one step = build pass + dense passes (0 unless profiling; no further launch is counted)
     ctx->total_ms += build_ms;
     // (3) ids of the result rows (column 0, in insertion order) -> key values
@@ -467,17 +483,20 @@ qe_result *run_groupby_hashed(qe_ctx *ctx, const qe_batch *batch, const Plan &pl
             QE_HIP(hipStreamSynchronize(ctx->stream));
             const unsigned int *hc = (const unsigned int *)ctx->h_ctrl;
             if (hc[1] == 4) {   // the keys do not fit the LDS table: dense ids from now on (this execution included)
+                stats_abandoned(ctx);
                 plan.use_ids = true;
                 if (try_ids()) return r;
                 continue;
             }
             collect_time(ctx);
             if (hc[1] != 0) {   // more than half full (or a probe sequence ran out): a bigger table, again
+                stats_abandoned(ctx);
                 if (C >= (1ll << 28)) fail(QE_ERR_UNSUPPORTED, "GROUP BY produced more than 2^27 groups");
                 C *= 8;
                 continue;
             }
             plan.hash_capacity = C;
+            stats_route(ctx, QE_GROUPBY_ROUTE_HASHED, C, 0);
             const int64_t used = hc[0];
             if (used > knobs().ids_from && ids_allowed && !plan.ids_overflow) plan.use_ids = true;   // the next executions of this plan
             PoolScratch dense_scratch(ctx);   // (goes back to the pool before the table)
@@ -492,6 +511,7 @@ qe_result *run_groupby_hashed(qe_ctx *ctx, const qe_batch *batch, const Plan &pl
             break;
         }
     }
+    if (n == 0) stats_route(ctx, QE_GROUPBY_ROUTE_HASHED, 0, 0);
     return finish_hashed_groups(ctx, cg, dense.data(), m, agg_fns, nagg);
 }
 
@@ -516,6 +536,7 @@ qe_result *run_groupby_hp(qe_ctx *ctx, const qe_batch *batch, const std::shared_
         for (int j = 0; j < P; j++) largest = std::max(largest, pp.start[j + 1] - pp.start[j]);
         if (m_records > (1ull << 22) && largest > 3 * (m_records / (unsigned long long)P) + 65536) {
             *skewed = true;
+            stats_abandoned(ctx);
             bracket_close(ctx);   // (the bracket the caller reads must be closed)
             if (ctx->opts.profile) QE_HIP(hipStreamSynchronize(ctx->stream));
             collect_time(ctx);
@@ -543,10 +564,15 @@ qe_result *run_groupby_hp(qe_ctx *ctx, const qe_batch *batch, const std::shared_
         QE_HIP(hipStreamSynchronize(ctx->stream));
         collect_time(ctx);
         const unsigned int *hc = (const unsigned int *)ctx->h_ctrl;
-        if (hc[1] != 0) return nullptr;   // 6: some partition's table filled up
+        if (hc[1] != 0) {   // 6: some partition's table filled up
+            stats_abandoned(ctx);
+            return nullptr;
+        }
         m = hc[0];
-        if (m >= (debug_bit(ctx, kDbgGroupsOnDevice) ? 1 : knobs().groups_on_device_from) && (int)cg.keys.size() <= 4 && nagg <= 8)
+        if (m >= (debug_bit(ctx, kDbgGroupsOnDevice) ? 1 : knobs().groups_on_device_from) && (int)cg.keys.size() <= 4 && nagg <= 8) {
+            stats_route(ctx, QE_GROUPBY_ROUTE_HASH_PARTITIONED_DEVICE, cg.part_groups, P);
             return finish_hashed_groups_on_device(ctx, cg, d_out, m, batch->nrows, agg_fns, nagg);
+        }
         if (m > 0) {
             dense = (uint64_t *)ctx->pinned.alloc((size_t)m * HW * 8);
             QE_HIP(hipMemcpyAsync(dense, d_out, (size_t)m * HW * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -557,6 +583,7 @@ qe_result *run_groupby_hp(qe_ctx *ctx, const qe_batch *batch, const std::shared_
         QE_HIP(hipStreamSynchronize(ctx->stream));
         collect_time(ctx);
     }
+    stats_route(ctx, QE_GROUPBY_ROUTE_HASH_PARTITIONED_HOST, cg.part_groups, P);
     return finish_hashed_groups(ctx, cg, dense, m, agg_fns, nagg);
 }
 
@@ -618,25 +645,31 @@ qe_result *run_groupby_hashed_route(const AggregateCall &q, const std::shared_pt
     const int64_t n = batch->nrows;
     const bool hp_possible = !hp_never && !plan->hp_failed && n > 0 && n < (1ll << 32) && q.nkeys <= 4 && q.nagg <= 8;
     const int max_shift = hp_max_shift(q, plan->cg);
+    // ONE workgroup aggregates a partition (128 partitions left half the chip idle: 21.8 ms for the aggregation of 1 B
+    // records).  Fewer partitions make longer runs per scatter tile -- less padding to whole lines --, more partitions keep
+    // the tables sparse.  Buckets for ~16x the keys seen (Knobs::hp_fill), 256 .. 4096 per partition.
+    // few partitions = long runs per scatter tile = little padding, and the probe loop tolerates full tables better than the
+    // scatter tolerates short runs (1 M keys, 1 B rows: 512 partitions half full 24.6 ms, 1024 partitions a quarter full
+    // 37.1 ms; 500 000 keys: 256 partitions half full 22.6 ms, 512 a quarter full 18.3 ms): 256 partitions up to 30 %, 512
+    // up to 50 %, 1024 beyond
+    struct HpSize { int P, shift; };
+    auto size_for = [&](int64_t known_keys) {
+        const int64_t keys_seen = std::max<int64_t>(known_keys, 1);
+        HpSize z{keys_seen * 10 <= ((int64_t)256 << max_shift) * 3 ? 256 : keys_seen * 2 <= ((int64_t)512 << max_shift) ? 512 : 1024, 8};
+        if (hp_forced && known_keys <= 0) z.P = 64;
+        if (kn.hp_parts >= 2) z.P = kn.hp_parts;
+        while (z.shift < max_shift && ((int64_t)z.P << z.shift) < keys_seen * kn.hp_fill) z.shift++;
+        if (kn.hp_shift >= 6) z.shift = kn.hp_shift;
+        return z;
+    };
+    HpSize overflowed{0, 0};   // partitions that were sized from a key count and overflowed in this execution
     if (hp_possible && (hp_forced || (plan->known_keys >= kn.hp_from && n >= (4ll << 20)))) {
-        // ONE workgroup aggregates a partition (128 partitions left half the chip idle: 21.8 ms for the aggregation of 1 B
-        // records).  Fewer partitions make longer runs per scatter tile -- less padding to whole lines --, more partitions keep
-        // the tables sparse.  Buckets for ~16x the keys seen (Knobs::hp_fill), 256 .. 4096 per partition.
-        const int64_t keys_seen = std::max<int64_t>(plan->known_keys, 1);
-        // few partitions = long runs per scatter tile = little padding, and the probe loop tolerates full tables better than the
-        // scatter tolerates short runs (1 M keys, 1 B rows: 512 partitions half full 24.6 ms, 1024 partitions a quarter full
-        // 37.1 ms; 500 000 keys: 256 partitions half full 22.6 ms, 512 a quarter full 18.3 ms): 256 partitions up to 30 %, 512
-        // up to 50 %, 1024 beyond
-        int P = keys_seen * 10 <= ((int64_t)256 << max_shift) * 3 ? 256 : keys_seen * 2 <= ((int64_t)512 << max_shift) ? 512 : 1024;
-        if (hp_forced && plan->known_keys <= 0) P = 64;
-        if (kn.hp_parts >= 2) P = kn.hp_parts;
-        int shift = 8;
-        while (shift < max_shift && ((int64_t)P << shift) < keys_seen * kn.hp_fill) shift++;
-        if (kn.hp_shift >= 6) shift = kn.hp_shift;
-        if (qe_result *r = try_hp(q, plan, P, shift)) return r;
+        const HpSize z = size_for(plan->known_keys);
+        if (qe_result *r = try_hp(q, plan, z.P, z.shift)) return r;
         // some partition's table filled up: with 1024 partitions there is nothing larger to try; otherwise the run below
         // reports how many keys there are and the next execution sizes its partitions from that
-        if (P >= 1024) plan->hp_failed = true;
+        if (z.P >= 1024) plan->hp_failed = true;
+        else if (plan->known_keys > 0 && kn.hp_parts < 2 && kn.hp_shift < 6) overflowed = z;
     }
     // The FIRST execution of a plan does not know its keys.  The LDS tables and the id build find out cheaply that there are
     // many (their launches stop at once when a table fills up: more than 32 768 keys fill the id build's first table); from
@@ -651,6 +684,13 @@ qe_result *run_groupby_hashed_route(const AggregateCall &q, const std::shared_pt
         out = run_groupby_hashed(ctx, batch, *plan, q.filter, q.exprs, q.agg_fns, q.nagg, nullptr);   // more keys than 1024 tables hold
     }
     if (out) plan->known_keys = out->count;
+    // .. unless that count sizes the very partitions that have just overflowed (the count was exact already: these keys crowd
+    // into one partition whatever its table): every later execution would repeat count pass, scatter pass and the abandoned
+    // aggregation before it falls back -- the plan gives the form up
+    if (out && overflowed.P > 0) {
+        const HpSize again = size_for(plan->known_keys);
+        if (again.P == overflowed.P && again.shift == overflowed.shift) plan->hp_failed = true;
+    }
     ctx->last_form = QE_FORM_GROUPBY_HASHED;
     return out;
 }
@@ -660,6 +700,7 @@ qe_result *run_groupby_hashed_route(const AggregateCall &q, const std::shared_pt
 namespace qe {
 
 qe_result *run_groupby(const AggregateCall &q) {
+    q.ctx->groupby_stats.store(0, 0, 0, 0);
     auto plan = get_plan(q.ctx, q.batch, q.request());
     if (plan->cg.hashed) return run_groupby_hashed_route(q, plan);
     qe_result *out = run_groupby_dense(q.ctx, q.batch, plan, q.agg_fns, q.nagg);
@@ -743,5 +784,7 @@ int32_t qe_filter_groupby(qe_ctx *ctx, const qe_batch *batch, const qe_expr *fil
         *out = run_groupby({ctx, batch, filter, keys, nkeys, exprs, agg_fns, nagg});
     });
 }
+
+int32_t qe_ctx_last_groupby_stats(const qe_ctx *ctx, int64_t out[4]) { return last_stats(ctx, &qe_ctx::groupby_stats, out); }
 
 }  // extern "C"

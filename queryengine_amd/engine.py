@@ -197,6 +197,14 @@ class Context:
         words = self._last_stats(self._lib.qe_ctx_last_sort_stats)
         return {"path": "select" if words[0] == 1 else "sort", "sorted_rows": words[1], "radix_passes": words[2], "select_passes": words[3]}
 
+    def last_groupby_stats(self) -> dict:
+        """qe_ctx_last_groupby_stats: what the last filter_groupby on this context did -- the route that produced the result (a
+        name of native.GROUPBY_ROUTES), the launches it abandoned and repeated another way, the capacity that sufficed (table
+        entries, buckets or groups per partition: by route) and the partitions of the partitioned passes (0: none ran)."""
+        st = self._last_stats(self._lib.qe_ctx_last_groupby_stats, ("route", "abandoned", "capacity", "partitions"))
+        st["route"] = N.GROUPBY_ROUTES[st["route"]]
+        return st
+
     def join_build(self, side, key_cols: Sequence[int]) -> "JoinTable":
         """qe_join_build: the hash table of an equi-join over the key columns of `side` (a Result or a DeviceBatch)."""
         return JoinTable(self, side, key_cols)

@@ -29,6 +29,9 @@ AGG_MIN, AGG_MAX, AGG_SUM, AGG_COUNT, AGG_AVG = range(5)
 COMM_ID_BYTES = 128
 FORM_RING, FORM_TWO_PASS, FORM_DENSE, FORM_PER_NODE, FORM_NO_FILTER, FORM_LOCAL = range(6)
 FORM_GROUPBY_DENSE, FORM_GROUPBY_HASHED, FORM_GROUPBY_HASH_PARTITIONED = 8, 9, 10
+# QE_GROUPBY_ROUTE_* of qe_ctx_last_groupby_stats, by value
+GROUPBY_ROUTES = ("none", "dense_lds", "dense_key_range", "dense_global", "hashed", "dense_ids", "hash_partitioned_host",
+                  "hash_partitioned_device")
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = range(4)
 WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_SUM, WIN_COUNT, WIN_MIN, WIN_MAX, WIN_AVG, WIN_LAG, WIN_LEAD = range(10)
 WIN_FIRST_VALUE, WIN_LAST_VALUE = 10, 11        # qe_result_window_frames only
@@ -152,6 +155,7 @@ SYMBOLS = [
                                         C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)]),
     ("qe_filter_groupby", C.c_int32, [_P, _P, _P, C.POINTER(_P), C.c_int32, C.POINTER(_P), C.POINTER(C.c_int32), C.c_int32, C.POINTER(_P)]),
     ("qe_filter_groupby_prepare", C.c_int32, [_P, _P, _P, C.POINTER(_P), C.c_int32, C.POINTER(_P), C.POINTER(C.c_int32), C.c_int32]),
+    ("qe_ctx_last_groupby_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_filter_aggregate_prepare", C.c_int32, [_P, _P, _P, C.POINTER(_P), C.POINTER(C.c_int32), C.c_int32]),
     ("qe_result_count", C.c_int64, [_P]),
     ("qe_result_ncols", C.c_int32, [_P]),
