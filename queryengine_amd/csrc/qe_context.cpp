@@ -436,6 +436,15 @@ int32_t qe_batch_ncols(const qe_batch *b) { return b ? (int32_t)b->cols.size() :
 int32_t qe_batch_column_type(const qe_batch *b, int32_t col) {
     return (b && col >= 0 && col < (int32_t)b->cols.size()) ? b->cols[col].type : -1;
 }
+int32_t qe_batch_column_nullable(const qe_batch *b, int32_t col) {
+    if (!b || col < 0 || col >= (int32_t)b->cols.size()) return -1;
+    return b->cols[(size_t)col].validity ? 1 : 0;
+}
+int32_t qe_batch_column_dict(const qe_batch *b, int32_t col, qe_dict **out) {
+    if (!b || !out || col < 0 || col >= (int32_t)b->cols.size() || !b->cols[(size_t)col].dict) return QE_ERR_INVALID_ARG;
+    *out = new qe_dict{b->cols[(size_t)col].dict};
+    return QE_OK;
+}
 
 int32_t qe_batch_column_to_host(qe_ctx *ctx, const qe_batch *b, int32_t col, int64_t row_begin, int64_t nrows,
                                 void *data_out, uint64_t *validity_out) {

@@ -21,7 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "qe_internal.h"
+#include "qe_exec.h"
 
 struct qe_csv_table {
     int64_t nrows = 0;
@@ -152,26 +152,42 @@ bool next_record(const char *d, size_t n, size_t &pos, std::vector<Field> &field
     }
 }
 
+namespace {
+
+// the bytes of a field of the record that next_record has just read
+void field_text(const char *d, const Field &f, const std::string &unq, const std::vector<std::pair<size_t, size_t>> &span, const char *&p, size_t &n) {
+    if (f.quoted) { p = unq.data() + span[f.begin].first; n = span[f.begin].second - span[f.begin].first; }
+    else { p = d + f.begin; n = f.end - f.begin; }
+}
+
+}  // namespace
+
+// The header: the first non-empty record from `pos` on (withFirstRecordAsHeader + withIgnoreEmptyLines); `pos` advances
+// past it.  Returns the field index of every name, -1 where the header does not hold it (everywhere, when there is no header).
+std::vector<int> header_fields(const char *d, size_t n, size_t &pos, const char *const *names, int32_t nfields) {
+    std::vector<int> idx((size_t)nfields, -1);
+    std::vector<Field> rec;
+    std::string unq;
+    std::vector<std::pair<size_t, size_t>> span;
+    bool empty = false;
+    while (next_record(d, n, pos, rec, unq, span, empty)) {
+        if (empty) continue;
+        for (int32_t k = 0; k < nfields; k++)
+            for (size_t i = 0; i < rec.size(); i++) {
+                const char *p; size_t m;
+                field_text(d, rec[i], unq, span, p, m);
+                // a duplicated header name resolves to its LAST occurrence: commons-csv 1.8 (CSVFormat.DEFAULT allows
+                // duplicates) fills its header map with put(), so a later column replaces an earlier one of the same name
+                if (m == std::strlen(names[k]) && std::memcmp(p, names[k], m) == 0) idx[(size_t)k] = (int)i;
+            }
+        break;
+    }
+    return idx;
+}
+
 }  // namespace qe
 
 using namespace qe;
-
-template <typename F>
-static int32_t guarded_csv(qe_ctx *ctx, F &&f) {
-    try {
-        f();
-        return QE_OK;
-    } catch (const Error &e) {
-        if (ctx) ctx->last_error = e.msg;
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        if (ctx) ctx->last_error = "host out of memory";
-        return QE_ERR_OOM;
-    } catch (const std::exception &e) {
-        if (ctx) ctx->last_error = e.what();
-        return QE_ERR_INTERNAL;
-    }
-}
 
 extern "C" {
 
@@ -179,7 +195,7 @@ int32_t qe_csv_parse(qe_ctx *ctx, const char *data, size_t nbytes, int32_t nfiel
                      qe_csv_table **out) {
     if (!ctx || !out || (!data && nbytes) || nfields < 0 || (nfields > 0 && (!names || !types))) return QE_ERR_INVALID_ARG;
     *out = nullptr;
-    return guarded_csv(ctx, [&] {
+    return guarded(ctx, [&] {
         std::unique_ptr<qe_csv_table> t(new qe_csv_table());
         t->cols.resize((size_t)nfields);
         for (int32_t k = 0; k < nfields; k++) {
@@ -195,31 +211,10 @@ int32_t qe_csv_parse(qe_ctx *ctx, const char *data, size_t nbytes, int32_t nfiel
         std::vector<std::pair<size_t, size_t>> span;
         size_t pos = 0;
         bool empty = false;
-        auto text = [&](const Field &f, const char *&p, size_t &n) {
-            if (f.quoted) { p = unq.data() + span[f.begin].first; n = span[f.begin].second - span[f.begin].first; }
-            else { p = data + f.begin; n = f.end - f.begin; }
-        };
-        // header: the first non-empty record (withFirstRecordAsHeader + withIgnoreEmptyLines)
-        std::vector<int> idx((size_t)nfields, -1);
-        bool have_header = false;
-        while (next_record(data, nbytes, pos, rec, unq, span, empty)) {
-            if (empty) continue;
-            have_header = true;
-            for (int32_t k = 0; k < nfields; k++) {
-                for (size_t i = 0; i < rec.size(); i++) {
-                    const char *p; size_t n;
-                    text(rec[i], p, n);
-                    // a duplicated header name resolves to its LAST occurrence: commons-csv 1.8 (CSVFormat.DEFAULT allows
-                    // duplicates) fills its header map with put(), so a later column replaces an earlier one of the same name
-                    if (n == std::strlen(names[k]) && std::memcmp(p, names[k], n) == 0) idx[(size_t)k] = (int)i;
-                }
-            }
-            break;
-        }
+        const std::vector<int> idx = header_fields(data, nbytes, pos, names, nfields);
         for (int32_t k = 0; k < nfields; k++)
             if (idx[(size_t)k] < 0)   // CsvSourceOperator.kt:27-28
                 fail(QE_ERR_INVALID_ARG, std::string("projected field ") + names[k] + " not found in csv headers");
-        (void)have_header;
         int64_t row = 0;
         while (next_record(data, nbytes, pos, rec, unq, span, empty)) {
             if (empty) continue;
@@ -227,7 +222,7 @@ int32_t qe_csv_parse(qe_ctx *ctx, const char *data, size_t nbytes, int32_t nfiel
                 qe_csv_table::Col &c = t->cols[(size_t)k];
                 const char *p = nullptr;
                 size_t n = 0;
-                if ((size_t)idx[(size_t)k] < rec.size()) text(rec[(size_t)idx[(size_t)k]], p, n);
+                if ((size_t)idx[(size_t)k] < rec.size()) field_text(data, rec[(size_t)idx[(size_t)k]], unq, span, p, n);
                 const bool is_null = n == 0;   // missing trailing field or isNullOrEmpty (:59-62)
                 if (c.type == QE_DOUBLE) {
                     double v = 0.0;
@@ -275,7 +270,7 @@ int32_t qe_csv_parse_file(qe_ctx *ctx, const char *path, int32_t nfields, const 
     if (!ctx || !path || !out) return QE_ERR_INVALID_ARG;
     *out = nullptr;
     std::vector<char> buf;
-    int32_t st = guarded_csv(ctx, [&] {
+    int32_t st = guarded(ctx, [&] {
         FILE *f = std::fopen(path, "rb");
         if (!f) fail(QE_ERR_INVALID_ARG, std::string("cannot open ") + path + ": " + std::strerror(errno));
         struct Closer { FILE *f; ~Closer() { std::fclose(f); } } closer{f};

@@ -24,6 +24,8 @@
 //                    left row, the output step
 //   qe_range.cpp     the range join of two results: a key sort over (by.., lo) and one over (by.., hi), two ordinals per left
 //                    row, a 64-bit scan of the counts, the load-balanced expansion into row pairs, the output step
+//   qe_csv_device.cpp  CSV text parsed on the device: the text sources and their upload, the passes as steps of one driver,
+//                    the field packer behind the dictionary and the patch list, one body for both entry points
 #pragma once
 
 #include <memory>

@@ -54,7 +54,7 @@ int promote_type(int a, int b);
 const char *type_name(int t);
 const char *fn_name(int fn);
 
-// ---- CSV host parser (qe_csv.cpp), shared with the device parser (qe_csv_device.hip) ----------------------------------
+// ---- CSV host parser (qe_csv.cpp), shared with the host side of the device parser (qe_csv_device.cpp) ------------------
 // java.lang.Double.parseDouble; false for what Java rejects
 bool java_parse_double(const char *p, size_t n, double &out);
 // one field of a record: [begin, end) of the text, or (quoted) begin = index into the unquoted spans
@@ -62,6 +62,9 @@ struct Field { size_t begin, end; bool quoted; };
 // one record at `pos` (advanced past its line end); false at end of input; throws Error on a malformed quoted field
 bool next_record(const char *d, size_t n, size_t &pos, std::vector<Field> &fields, std::string &unq,
                  std::vector<std::pair<size_t, size_t>> &unq_span, bool &empty_line);
+// the header, the first non-empty record from `pos` on (advanced past it): per name the index of the LAST field that
+// spells it, -1 where none does; throws what next_record throws
+__attribute__((visibility("hidden"))) std::vector<int> header_fields(const char *d, size_t n, size_t &pos, const char *const *names, int32_t nfields);
 
 // ---- dictionaries ----------------------------------------------------------------------
 struct DictData {

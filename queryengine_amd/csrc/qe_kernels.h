@@ -331,6 +331,73 @@ struct RangeExpandArgs {
 };
 void launch_range_expand(hipStream_t s, const RangeExpandArgs &a);
 
+// ---- CSV text parsed on the device (qe_csv_device.hip) ----
+#pragma GCC visibility push(hidden)   // qe_csv_device.cpp alone calls these
+constexpr int kCsvTile = 4096;   // text bytes per wave in the structure passes; the text buffer is zero-padded to whole tiles
+// flags word: what the passes found that the host parser would read differently
+enum { QE_CSV_QUOTE_RULE = 1, QE_CSV_BAD_NUMBER = 2, QE_CSV_PATCH_OVERFLOW = 4 };
+// tile_quotes[t] = the '"' bytes of tile t
+void launch_csv_quote_count(hipStream_t s, const unsigned char *text, long long ntiles, long long *tile_quotes);
+// The non-empty records of the n text bytes, from the scanned quote counts.  write false: tile_rows[t] = records that start in
+// tile t, and QE_CSV_QUOTE_RULE where a '"' is not the enclosing quote of a field; true: rec_start[row] = first byte of the
+// record, through the scanned tile_rows
+void launch_csv_records(hipStream_t s, bool write, const unsigned char *text, long long n, long long ntiles, const long long *tile_quotes,
+                        long long *tile_rows, long long *rec_start, unsigned int *flags);
+// The fields of one projected column: row r holds the lenesc[r] >> 1 content bytes from text + begin[r], and lenesc[r] & 1 says
+// that they hold "" escapes.  No byte = NULL (empty, "" or missing).
+struct CsvFields {
+    const unsigned char *text;
+    long long nrows;
+    long long *begin;
+    unsigned int *lenesc;
+};
+// all: the fields of all ncols columns, column k at k * nrows, written from the record starts
+struct CsvSpanArgs {
+    CsvFields all;
+    long long n;                            // text bytes
+    const long long *rec_start;
+    const int *field_of;                    // per projected column: field index in the record
+    int ncols, max_field;
+};
+void launch_csv_spans(hipStream_t s, const CsvSpanArgs &a);
+// DOUBLE: values (0 under a NULL) and validity; a field that is no number raises QE_CSV_BAD_NUMBER, one that the device
+// leaves undecided goes to patch_rows, QE_CSV_PATCH_OVERFLOW past patch_cap.  BOOLEAN: value and validity bitmaps.
+// *any_null is raised when a row is NULL
+struct CsvConvArgs {
+    CsvFields f;
+    void *data;
+    unsigned long long *validity;
+    unsigned int *any_null, *flags;
+    long long *patch_rows;
+    unsigned int *patch_count, patch_cap;
+};
+void launch_csv_convert_double(hipStream_t s, const CsvConvArgs &a);
+void launch_csv_convert_bool(hipStream_t s, const CsvConvArgs &a);
+// data[rows[i]] = values[i], i < n
+void launch_csv_scatter_f64(hipStream_t s, double *data, const long long *rows, const double *values, long long n);
+// STRING: the dictionary of a column and the codes of its rows, in three steps with a scan between them
+struct CsvDictArgs {
+    CsvFields f;
+    unsigned long long *hash;               // per row: FNV-1a of the unescaped bytes
+    unsigned int *slots;                    // open-addressing table of mask + 1 entries (0xFFFFFFFF: free): the row that represents the string
+    unsigned int *first;                    // .. the smallest row holding it (0xFFFFFFFF on entry)
+    unsigned long long mask;
+    unsigned int *row_slot;                 // per row: its entry
+    long long *rank;                        // per row: 1 if the row is the first of its string, then (scanned) the code it gives that string
+    int *codes;
+    long long *dist_row;                    // per code: the first row
+    long long *dist_len;                    // per code: unescaped bytes
+    unsigned long long *validity;
+    unsigned int *any_null;
+};
+void launch_csv_dict_build(hipStream_t s, const CsvDictArgs &a);   // hash, validity, table, rank (unscanned)
+void launch_csv_dict_codes(hipStream_t s, const CsvDictArgs &a);   // rank scanned: codes, dist_row, dist_len
+// len[i] = unescaped bytes of field rows[i], i < n
+void launch_csv_field_len(hipStream_t s, const CsvFields &f, const long long *rows, long long n, long long *len);
+// the unescaped bytes of field rows[i] at packed + off[i], i < n
+void launch_csv_pack_fields(hipStream_t s, const CsvFields &f, const long long *rows, long long n, const long long *off, unsigned char *packed);
+#pragma GCC visibility pop
+
 // ---- gathers through u32 row ids (qe_kernels.hip): ORDER BY, window, join, per-node ----
 // grid caps, in blocks of 256 threads: every caller's, and the join's output columns (with the narrow cap the probe was 0.4 to
 // 0.6 % slower than before in every interleaved run, with the wide one it is not: profiles/result_builder_refactor_summary.txt)

@@ -1,7 +1,8 @@
-"""The device CSV parser (qe_csv_device.hip, qe_csv_number.h) at the sizes and inputs where its code changes
+"""The device CSV parser (qe_csv_device.cpp / .hip, qe_csv_number.h) at the sizes and inputs where its code changes
 path: the decimal -> double converter as DEVICE code on the corpus of tests/test_csv_device_cpu.py, the recursive scan at its
 third level, the dictionary beyond one workgroup of the scan (2048 entries) and one block of the pack kernel (256), texts of
-2047 / 2048 / 2049 tiles and of length 0, 1, 4095 mod 4096 under every kind of last byte, and the patch list's overflow.
+2047 / 2048 / 2049 tiles and of length 0, 1, 4095 mod 4096 under every kind of last byte, and the patch list: full, one
+field past full, and its fields as the shared packer brings them to the host.
 
 Every test compares the device batch with the host parser (qe_csv_parse + qe_csv_pin) through ``check_parity``: bit-equal
 data words, validity words, nullability and dictionaries.  Nothing here has a tolerance.  What a test is about (a row count,
@@ -17,10 +18,10 @@ from queryengine_amd.csv_table import read_csv_device
 
 pytestmark = pytest.mark.gpu
 
-TILE = 4096                      # kTile: text bytes per wave of the structure passes
+TILE = 4096                      # kCsvTile: text bytes per wave of the structure passes
 SCAN_BLOCK = 1024                # kScanBlock (qe_scan.h): elements per workgroup of exclusive_scan, block sums per trip of its carry scan
 SCAN_PER = 2048                  # elements per workgroup of the parser's former recursive scan: its seams stay in the cases
-PACK_BLOCK = 256                 # distinct strings per block of dict_pack_kernel
+PACK_BLOCK = 256                 # fields per block of dict_pack_kernel: the distinct strings, or the patch list
 PATCH_CAP = 1 << 20              # undecided fields of one column that the patch list holds
 # scan() works on n + 1 elements (the total lands behind the last): exclusive_scan in workgroups of kScanBlock, whose sums ONE
 # workgroup scans in trips of kScanBlock with a carry.  Its second trip begins at n + 1 = 1024 * 1024 + 1.
@@ -39,7 +40,7 @@ def field(s):
 
 
 # ---- 1. the converter on the device ---------------------------------------------------------------------------------------
-MAX_HARD = 1000                  # each patched field costs three small device-to-host copies
+MAX_HARD = 1000                  # undecidable strings kept: few enough that the test below stays one about the device's converter
 
 
 @pytest.fixture(scope="module")
@@ -270,8 +271,7 @@ def test_text_lengths_that_do_not_divide_among_the_fill_threads(gpu_ctx, tmp_pat
 # ---- 5. patch overflow -----------------------------------------------------------------------------------------------------
 def test_patch_list_overflow_falls_back(gpu_ctx):
     """One undecided field more than the patch list holds: the whole input goes to the host, and the context is good for the
-    next parse.  Exactly PATCH_CAP undecided fields -- the most the device path patches -- are not tested: the path fetches
-    every patched field with three small copies, and three million of them take far longer than a test may."""
+    next parse."""
     lits = ["0x1p3", "0x1.8p1", "-0x1.fffffffffffffp1023", "0X.8P-1d", "0x1p-1074", "0xAp0", " 0x.1p+4 "]
     n = PATCH_CAP + 1
     rows = (lits * (n // len(lits) + 1))[:n]
@@ -281,3 +281,28 @@ def test_patch_list_overflow_falls_back(gpu_ctx):
     assert st.host_fallback == 1 and st.nrows == n
     st = check_parity(gpu_ctx, b"x\n0x1p3\n1.5\n\n2e400\n", sch)
     assert st.host_fallback == 0 and st.host_patched_fields == 1 and st.nrows == 3
+
+
+def test_patch_list_exactly_full(gpu_ctx):
+    """PATCH_CAP undecided fields, the most the device path patches.  Row i is the hexadecimal literal of i: every value is
+    distinct and the lengths run from 1 to 5 digits, so a wrong offset, slice or scatter slot is a wrong value."""
+    n = PATCH_CAP
+    text = ("x\n" + "".join(f"0x{i:x}p0\n" for i in range(n))).encode()
+    st = check_parity(gpu_ctx, text, Schema([Field("x", D)]))
+    assert st.host_fallback == 0 and st.host_patched_fields == n and st.nrows == n
+
+
+def test_patched_fields_written_in_several_ways(gpu_ctx):
+    """One column whose undecidable fields are plain, enclosed, and enclosed with spaces around the literal: the packer hands
+    the host the content without the quotes, in the order of the patch list, which is not the row order.  Decidable rows
+    stand between them.  More than one block of the length and pack kernels."""
+    hard = ["0x1p3", '"0x1p3"', '" 0x1p3 "', "123456789012345678901234567", '"123456789012345678901234567"',
+            '" 123456789012345678901234567 "']
+    cells = []
+    for i in range(700):
+        cells += [hard[i % len(hard)] if i % 5 else f'"0x{i:x}p-{i % 9}"', "1e3", '""', f"{i}.25"][: 2 + i % 3]   # ("": NULL)
+    nhard = sum(1 for c in cells if "x" in c or len(c) > 20)
+    assert nhard == 700 > 2 * PACK_BLOCK and len(cells) > 2 * nhard
+    text = ("x\n" + "".join(c + "\n" for c in cells) + "0x1p3").encode()
+    st = check_parity(gpu_ctx, text, Schema([Field("x", D)]))
+    assert st.host_fallback == 0 and st.host_patched_fields == nhard + 1 and st.nrows == len(cells) + 1
