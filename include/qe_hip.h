@@ -402,11 +402,21 @@ int32_t qe_ctx_last_sort_stats(const qe_ctx *ctx, int64_t out[4]);
  *   QE_JOIN_LEFT   the same, plus one row for every probe row without a match, in its place, every build column NULL
  *   QE_JOIN_SEMI   every probe row with at least one match, once, in probe order
  *   QE_JOIN_ANTI   every probe row without a match (a NULL key is no match), in probe order
- * SEMI and ANTI take no build columns (nbuild_out == 0).
+ *   QE_JOIN_RIGHT  a HEAD, exactly the rows of QE_JOIN_INNER in their order, then a TAIL: every build row that no probe row of
+ *                  THIS call matched, once, in ascending build row index, every probe column of it NULL (validity 0, value
+ *                  zero).  A build row with a NULL in a key matches nothing, so it is always in the tail
+ *   QE_JOIN_FULL   the same with the rows of QE_JOIN_LEFT as the head
+ * SEMI and ANTI take no build columns (nbuild_out == 0).  Zero rows on either side is an ordinary input: without probe rows
+ * the tail is the whole build side; without build rows RIGHT is empty and FULL is LEFT.
+ * The table is not changed by a probe: the marks of the matched build rows belong to the call (a bitmap over build rows in its
+ * scratch), so a table may be probed FULL by one side and then with any type by another.  The marks are set by integer ORs
+ * and read only after the pass that sets them; no atomic decides a position in the output.
  *
  * Columns: the listed probe columns, then the listed build columns; a column may be listed twice, a list may be empty,
  * but there must be at least one output column.  A STRING column carries its source's dictionary; nullability is that of
- * the source, and under LEFT every build column is nullable (an unmatched row: validity 0, value zero).  The result has
+ * the source, and under LEFT every build column is nullable (an unmatched row: validity 0, value zero); under RIGHT every
+ * probe column is nullable and the build columns are as the source, under FULL every column is nullable -- the schema follows
+ * from the inputs' schemas and the join type alone.  RIGHT / FULL with no probe columns is legal.  The result has
  * the layouts of every other result: qe_result_order_by_keys, qe_result_to_host, qe_result_concat, qe_gather take it.
  *
  * Lifetime: the table reads the build side's columns again at probe time, so the build input must outlive the table; the
@@ -416,9 +426,10 @@ int32_t qe_ctx_last_sort_stats(const qe_ctx *ctx, int64_t out[4]);
  * of range, paired key columns of different types, nkeys outside 1..4, a schema-only batch, an unknown join type, no
  * output column, build columns with SEMI / ANTI; QE_ERR_UNSUPPORTED for a side of more than 2^32 - 2 rows (rows are
  * uint32 with one sentinel, as in the sort); QE_ERR_HIP on a planning-only context; QE_ERR_OOM when the output does not
- * fit.  Output counts and offsets are 64-bit throughout.
+ * fit.  Output counts and offsets are 64-bit throughout (head + tail), and the tail's length is read back together with the
+ * head's: one read-back per call.  The values 4 to 7 of the join type are unassigned and rejected.
  * Known limit: the matches of ONE probe row are walked by one lane, so a probe key with very many matches is slow. */
-enum { QE_JOIN_INNER = 0, QE_JOIN_LEFT = 1, QE_JOIN_SEMI = 2, QE_JOIN_ANTI = 3 };
+enum { QE_JOIN_INNER = 0, QE_JOIN_LEFT = 1, QE_JOIN_SEMI = 2, QE_JOIN_ANTI = 3, QE_JOIN_RIGHT = 8, QE_JOIN_FULL = 9 };
 /* one side of a join: exactly one of the two is non-NULL */
 typedef struct { const qe_result *result; const qe_batch *batch; } qe_join_input;
 typedef struct qe_join_table qe_join_table;
@@ -432,8 +443,12 @@ int32_t qe_join_probe(qe_ctx *ctx, const qe_join_table *table, const qe_join_inp
                       const int32_t *probe_out_cols, int32_t nprobe_out,
                       const int32_t *build_out_cols, int32_t nbuild_out, qe_result **out);
 /* what the last qe_join_build / qe_join_probe of this context did: out[0] build rows in the table, out[1] probe rows,
- * out[2] output rows, out[3] longest candidate run one probe row scanned */
+ * out[2] output rows (RIGHT / FULL: head + tail), out[3] longest candidate run one probe row scanned */
 int32_t qe_ctx_last_join_stats(const qe_ctx *ctx, int64_t out[4]);
+/* the last RIGHT or FULL call of this context (zeros before the first; other join types leave it alone):
+ * out[0] 1 = qe_join_probe, 2 = qe_result_range_join; out[1] head rows; out[2] tail rows;
+ * out[3] build / right rows matched at least once.  out[2] + out[3] = rows of the build / right side. */
+int32_t qe_ctx_last_outer_stats(const qe_ctx *ctx, int64_t out[4]);
 
 /* ---- window functions over a result -------------------------------------------------------------------------
  * The reference has no windows (Query.g4); this is the step that answers a question about a row relative to its neighbours
@@ -730,7 +745,11 @@ int32_t qe_ctx_last_asof_stats(const qe_ctx *ctx, int64_t out[4]);
  * Join types (the values of the hash join's enum).  QE_JOIN_INNER: one row per (left row, matching right row).  QE_JOIN_LEFT:
  * the same, and one row in its place for every left row without a match, every right column of it NULL (validity 0, value
  * zero).  QE_JOIN_SEMI: every left row with at least one match, once.  QE_JOIN_ANTI: every left row without one (a NULL key
- * counts as no match).  SEMI and ANTI take no right columns (nright_out == 0).
+ * counts as no match).  SEMI and ANTI take no right columns (nright_out == 0).  QE_JOIN_RIGHT: a HEAD, exactly the rows of
+ * QE_JOIN_INNER in their order, then a TAIL: every right row that no left row of this call matched, once, in ascending right
+ * row index, every left column of it NULL (validity 0, value zero); a right row with a NULL by column or a NULL on matches
+ * nothing and is always in the tail.  QE_JOIN_FULL: the same with the rows of QE_JOIN_LEFT as the head.  Without left rows the
+ * tail is the whole right side; without right rows RIGHT is empty and FULL is LEFT.  The values 4 to 7 are unassigned.
  *
  * Order: left rows come out in input order; inside one left row the matches ascend by on(r) under the comparator, ties in
  * ascending right row index.  So with left_lo == left_hi, no strict end, nby == 0 and a key without NULLs the pairs and their
@@ -738,17 +757,19 @@ int32_t qe_ctx_last_asof_stats(const qe_ctx *ctx, int64_t out[4]);
  *
  * Columns: the listed left columns, then the listed right columns.  A column may be listed twice and either list may be empty,
  * but there is at least one output column.  A STRING column carries its source's dictionary (merged dictionaries are scratch
- * for the keys only); nullability is the source's, and under QE_JOIN_LEFT every right column is nullable.  `left` and `right`
- * may be the same handle.
+ * for the keys only); nullability is the source's, and under QE_JOIN_LEFT every right column is nullable, under QE_JOIN_RIGHT
+ * every left column, under QE_JOIN_FULL every column.  `left` and `right` may be the same handle.
  *
- * Determinism: the same inputs give the same bytes on every run and every context.  No atomic feeds a result byte (the one
- * atomic is an integer max for the stats).
+ * Determinism: the same inputs give the same bytes on every run and every context.  The atomics are an integer max for the
+ * stats and, under RIGHT / FULL, integer adds (how many intervals cover a position of the list of right rows) and integer ORs
+ * (the marks of the matched right rows), whose final values do not depend on arrival order; no atomic decides a position in
+ * the output.
  *
  * Sizes: counts and offsets of the output are 64-bit throughout; the output's size is read back once, as in the hash join,
- * together with the stats.
+ * together with the stats and the length of the tail.
  *
  * Limits and errors (*out = NULL): QE_ERR_INVALID_ARG for a null pointer (left_by / right_by may be null when nby == 0, a column
- * list when its count is 0), nby outside 0..7, a strict flag other than 0 or 1, a join_type outside the four, a negative column
+ * list when its count is 0), nby outside 0..7, a strict flag other than 0 or 1, a join_type outside the six, a negative column
  * count, no output column, right columns with SEMI or ANTI -- these are checked before either result is read -- a column out of
  * range, paired by columns of different types, a value column that is not DOUBLE, INT64 or INT32, value columns whose types
  * differ among the three, a STRING by column without a dictionary; QE_ERR_UNSUPPORTED for left rows + right rows > 2^32 - 2;
@@ -764,11 +785,13 @@ int32_t qe_ctx_last_asof_stats(const qe_ctx *ctx, int64_t out[4]);
  * right rows with a whole key before it.  Those right rows stand in the same order in both sorts, so the two ordinals index one
  * list and the matches of a left row are the entries between them.  A 64-bit scan of the per-row counts gives every left row
  * its first output row, and a load-balanced expansion -- a workgroup per tile of consecutive OUTPUT rows, a search per output
- * row, no lane walking one left row's matches -- writes the row pairs for the row gather every operator uses. */
+ * row, no lane walking one left row's matches -- writes the row pairs for the row gather every operator uses.  RIGHT / FULL: the
+ * matched right rows are the union of those index intervals; +1 / -1 at their ends in a difference array, one more scan and a
+ * marking pass give the bitmap of the matched right rows, and its complement, compacted, is the tail. */
 int32_t qe_result_range_join(qe_ctx *ctx, const qe_result *left, const qe_result *right,
                              const int32_t *left_by, const int32_t *right_by, int32_t nby,
                              int32_t left_lo, int32_t left_hi, int32_t right_on,
-                             int32_t lo_strict, int32_t hi_strict, int32_t join_type,   /* QE_JOIN_INNER / LEFT / SEMI / ANTI */
+                             int32_t lo_strict, int32_t hi_strict, int32_t join_type,   /* QE_JOIN_INNER / LEFT / SEMI / ANTI / RIGHT / FULL */
                              const int32_t *left_out, int32_t nleft_out,
                              const int32_t *right_out, int32_t nright_out, qe_result **out);
 /* what the last qe_result_range_join of this context did: out[0] left rows, out[1] right rows, out[2] output rows, out[3] the

@@ -61,10 +61,11 @@ internal object QeNative {
     val qe_join_build = handle("qe_join_build", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, ADDRESS)
     val qe_join_table_rows = handle("qe_join_table_rows", JAVA_LONG, ADDRESS)                         // build rows with a key
     val qe_join_table_free = handle("qe_join_table_free", null, ADDRESS, ADDRESS)
-    // ctx, table, probe side, int key_cols[nkeys], nkeys, join type (0 INNER, 1 LEFT, 2 SEMI, 3 ANTI), int probe_out[n], n,
+    // ctx, table, probe side, int key_cols[nkeys], nkeys, join type (0 INNER, 1 LEFT, 2 SEMI, 3 ANTI, 8 RIGHT, 9 FULL), int probe_out[n], n,
     // int build_out[m], m (0 for SEMI / ANTI), qe_result** -> status: rows in nested-loop order, probe side outside
     val qe_join_probe = handle("qe_join_probe", JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS)
     val qe_ctx_last_join_stats = handle("qe_ctx_last_join_stats", JAVA_INT, ADDRESS, ADDRESS)         // ctx, long[4]
+    val qe_ctx_last_outer_stats = handle("qe_ctx_last_outer_stats", JAVA_INT, ADDRESS, ADDRESS)       // ctx, long[4]: 1 hash / 2 range, head rows, tail rows, matched build / right rows
     // ---- window functions over a result (ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW inside the partition) ----
     // ctx, result, int partition_cols[npart], npart, qe_sort_key order[norder], norder, qe_window_fn fns[nfn] {int fn, int column,
     // long offset}, nfn (1..16), qe_result** -> status: every input column sorted by (partition, order), then one column per function

@@ -86,7 +86,7 @@ qe_result *run_asof(qe_ctx *ctx, const TwoSidedCall &q, int32_t left_on, int32_t
         lrows = kept;
         rrows = theirs;
     }
-    emit_joined(ctx, res.get(), nout, q.left->cols, q.left_out, q.nleft_out, lrows, q.right->cols, q.right_out, q.nright_out, rrows, !inner,
+    emit_joined(ctx, res.get(), nout, q.left->cols, q.left_out, q.nleft_out, lrows, q.right->cols, q.right_out, q.nright_out, rrows, false, !inner,
                 kGatherBlocks);
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));   // the key result and the scratch go back to the pool now

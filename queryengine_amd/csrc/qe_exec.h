@@ -197,7 +197,8 @@ struct TwoSidedCall {
     const int32_t *left_out, *right_out;
     int32_t nleft_out, nright_out, join_type;
 };
-constexpr uint32_t kJoinsPairs = 1u << QE_JOIN_INNER | 1u << QE_JOIN_LEFT, kJoinsAll = kJoinsPairs | 1u << QE_JOIN_SEMI | 1u << QE_JOIN_ANTI;
+constexpr uint32_t kJoinsPairs = 1u << QE_JOIN_INNER | 1u << QE_JOIN_LEFT, kJoinsOuter = 1u << QE_JOIN_RIGHT | 1u << QE_JOIN_FULL,
+                   kJoinsAll = kJoinsPairs | 1u << QE_JOIN_SEMI | 1u << QE_JOIN_ANTI | kJoinsOuter;
 // What can be said without reading either side (a caller's handle is only touched once this has returned): 0 to 7 by columns
 // with both lists there, option_error (the caller's verdict on its own flags, null: none), join_type among join_types (a
 // kJoins.. set), the out lists, "no output column", "a SEMI / ANTI join has no right columns".  All QE_ERR_INVALID_ARG.
@@ -245,14 +246,15 @@ struct SourceColumn {
 };
 // one more column of res: src gathered by rows[0..nout) (gather_column: max_blocks); no launch for nout == 0
 void emit_column(qe_ctx *ctx, qe_result *res, int64_t nout, const SourceColumn &src, const uint32_t *rows, bool force_nullable, int max_blocks);
-// The output step of a join: the listed left columns by lrows, then the listed right columns by rrows (nullable whatever
-// the source when right_nullable: the LEFT join's unmatched rows), into a result of nout rows.
+// The output step of a join: the listed left columns by lrows (nullable whatever the source when left_nullable: the tail of a
+// RIGHT / FULL join), then the listed right columns by rrows (nullable whatever the source when right_nullable: the unmatched
+// rows of a LEFT / FULL join), into a result of nout rows.
 template <typename L, typename R>
 void emit_joined(qe_ctx *ctx, qe_result *res, int64_t nout, const std::vector<L> &lcols, const int32_t *left_out, int32_t nleft_out,
                  const uint32_t *lrows, const std::vector<R> &rcols, const int32_t *right_out, int32_t nright_out, const uint32_t *rrows,
-                 bool right_nullable, int max_blocks) {
+                 bool left_nullable, bool right_nullable, int max_blocks) {
     res->cols.reserve((size_t)(nleft_out + nright_out));
-    for (int32_t i = 0; i < nleft_out; i++) emit_column(ctx, res, nout, lcols[(size_t)left_out[i]], lrows, false, max_blocks);
+    for (int32_t i = 0; i < nleft_out; i++) emit_column(ctx, res, nout, lcols[(size_t)left_out[i]], lrows, left_nullable, max_blocks);
     for (int32_t i = 0; i < nright_out; i++) emit_column(ctx, res, nout, rcols[(size_t)right_out[i]], rrows, right_nullable, max_blocks);
 }
 

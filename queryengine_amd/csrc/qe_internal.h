@@ -452,6 +452,7 @@ struct qe_ctx {
     qe::Stats4 set_stats;      // left rows, right rows, distinct tuples the sort found, STRING columns translated
     qe::Stats4 asof_stats;     // left rows, right rows, left rows that found a match, by partitions of the sort
     qe::Stats4 range_stats;    // left rows, right rows, output rows, most matches of one left row
+    qe::Stats4 outer_stats;    // the last RIGHT / FULL join: 1 hash / 2 range, head rows, tail rows, build / right rows matched
     qe::Stats4 groupby_stats;  // route (QE_GROUPBY_ROUTE_*), abandoned launches, capacity that sufficed, partitions
 };
 

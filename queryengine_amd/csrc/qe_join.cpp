@@ -171,7 +171,8 @@ qe_result *probe_table(qe_ctx *ctx, const qe_join_table *t, const qe_join_input 
     const char *who = "qe_join_probe";
     const Side side = side_of(in, who);
     if (!key_cols || nkeys != (int32_t)t->key_cols.size()) fail(QE_ERR_INVALID_ARG, std::string(who) + ": nkeys differs from the table's");
-    if (join_type < QE_JOIN_INNER || join_type > QE_JOIN_ANTI) fail(QE_ERR_INVALID_ARG, std::string(who) + ": unknown join type");
+    const bool outer = join_type == QE_JOIN_RIGHT || join_type == QE_JOIN_FULL;
+    if ((join_type < QE_JOIN_INNER || join_type > QE_JOIN_ANTI) && !outer) fail(QE_ERR_INVALID_ARG, std::string(who) + ": unknown join type");
     check_cols(side, key_cols, nkeys, who, "key");
     for (int32_t k = 0; k < nkeys; k++)
         if (side.cols[(size_t)key_cols[k]].type != t->build.cols[(size_t)t->key_cols[(size_t)k]].type)
@@ -179,13 +180,14 @@ qe_result *probe_table(qe_ctx *ctx, const qe_join_table *t, const qe_join_input 
                                          " on the probe side and " + type_name(t->build.cols[(size_t)t->key_cols[(size_t)k]].type) + " on the build side");
     check_cols(side, probe_out, nprobe_out, who, "probe output");
     check_cols(t->build, build_out, nbuild_out, who, "build output");
-    const bool pairs = join_type == QE_JOIN_INNER || join_type == QE_JOIN_LEFT;
+    const int32_t head_type = join_type == QE_JOIN_RIGHT ? QE_JOIN_INNER : join_type == QE_JOIN_FULL ? QE_JOIN_LEFT : join_type;   // the HEAD's
+    const bool pairs = head_type == QE_JOIN_INNER || head_type == QE_JOIN_LEFT;
     if (!pairs && nbuild_out != 0) fail(QE_ERR_INVALID_ARG, std::string(who) + ": a SEMI / ANTI join has no build columns");
     if (nprobe_out + nbuild_out < 1) fail(QE_ERR_INVALID_ARG, std::string(who) + ": no output column");
     if (side.nrows > kMaxSideRows) fail(QE_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 2 rows");
     need_device(ctx);
 
-    const int64_t n = side.nrows;
+    const int64_t n = side.nrows, nbuild = t->build.nrows;
     PoolScratch sc(ctx);
     std::vector<std::vector<int32_t>> tables;
     JoinProbeArgs pa{};
@@ -197,34 +199,54 @@ qe_result *probe_table(qe_ctx *ctx, const qe_join_table *t, const qe_join_input 
     pa.t.nkeys = nkeys;
     pa.t.mask = t->mask;
     pa.n = n;
-    pa.join_type = join_type;
+    pa.join_type = head_type;
     const int64_t nblocks = join_probe_blocks(n);
     pa.cnt = (uint32_t *)sc.alloc((size_t)n * 4);
     if (pairs) pa.first = (uint32_t *)sc.alloc((size_t)n * 4);
     pa.blocksum = (unsigned long long *)sc.alloc((size_t)nblocks * 8);
-    unsigned long long *d_ctl = (unsigned long long *)sc.alloc(16);   // [0] total, [1] longest walk (u32)
+    unsigned long long *d_ctl = (unsigned long long *)sc.alloc(32);   // [0] total, [1] longest walk (u32), [2] tail rows (RIGHT / FULL)
     pa.longest = (uint32_t *)(d_ctl + 1);
-    QE_HIP(hipMemsetAsync(d_ctl, 0, 16, ctx->stream));
+    QE_HIP(hipMemsetAsync(d_ctl, 0, 32, ctx->stream));
+    uint32_t *tail_prefix = nullptr;
+    if (outer && nbuild > 0) {   // the marks belong to this call: the table is not written
+        pa.matched = (unsigned long long *)sc.alloc(bitmap_bytes(nbuild));
+        QE_HIP(hipMemsetAsync(pa.matched, 0, bitmap_bytes(nbuild), ctx->stream));
+    }
     launch_join_count(ctx->stream, pa);
     launch_carry_scan<unsigned long long, 1024>(ctx->stream, pa.blocksum, nblocks, 1, d_ctl);   // 64-bit: the pairs may pass 2^32
-    unsigned long long h_ctl[2] = {0, 0};
-    QE_HIP(hipMemcpyAsync(h_ctl, d_ctl, 16, hipMemcpyDeviceToHost, ctx->stream));   // the one read-back: the output's size
+    if (pa.matched) {   // matched -> unmatched, and its ranks: the tail's length arrives with the head's
+        const int64_t nwords = bitmap_words(nbuild);
+        tail_prefix = (uint32_t *)sc.alloc((size_t)(nwords + 1) * 4);
+        uint32_t *sums = (uint32_t *)sc.alloc((size_t)scan_blocks(nwords + 1) * 4);
+        launch_join_unmatched(ctx->stream, pa.matched, nbuild);
+        bitmap_ranks(ctx->stream, (const uint64_t *)pa.matched, nullptr, nbuild, tail_prefix, sums, d_ctl + 2);
+    }
+    unsigned long long h_ctl[4] = {0, 0, 0, 0};
+    QE_HIP(hipMemcpyAsync(h_ctl, d_ctl, 32, hipMemcpyDeviceToHost, ctx->stream));   // the one read-back: the output's size
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));
     const int64_t total = (int64_t)h_ctl[0];   // at most 2^32 rows of at most 2^32 matches: fits; an output too large for the
                                                // device is reported by the pool below (QE_ERR_OOM)
+    const int64_t tail = (int64_t)h_ctl[2];
+    if (tail < 0 || tail > nbuild) fail(QE_ERR_INTERNAL, std::string(who) + ": " + std::to_string(tail) + " unmatched of " + std::to_string(nbuild) + " build rows");
+    const int64_t nout = total + tail;
 
-    ResultPtr res = new_result(ctx, total);
+    ResultPtr res = new_result(ctx, nout);
     pa.total = (unsigned long long)total;
-    pa.prow_out = (uint32_t *)sc.alloc((size_t)total * 4);
-    if (pairs) pa.brow_out = (uint32_t *)sc.alloc((size_t)total * 4);
+    pa.prow_out = (uint32_t *)sc.alloc((size_t)nout * 4);
+    if (pairs) pa.brow_out = (uint32_t *)sc.alloc((size_t)nout * 4);
     launch_join_write(ctx->stream, pa);
+    if (tail > 0) {   // the tail extends the two lists: no probe row, the unmatched build rows ascending
+        QE_HIP(hipMemsetAsync(pa.prow_out + total, 0xFF, (size_t)tail * 4, ctx->stream));
+        bitmap_positions(ctx->stream, (const uint64_t *)pa.matched, nullptr, nbuild, tail_prefix, pa.brow_out + total, tail, false);
+    }
 
-    emit_joined(ctx, res.get(), total, side.cols, probe_out, nprobe_out, pa.prow_out, t->build.cols, build_out, nbuild_out, pa.brow_out,
-                join_type == QE_JOIN_LEFT, kGatherBlocksWide);   // (no launch for no rows: launch_gather_rows returns at once, as before)
+    emit_joined(ctx, res.get(), nout, side.cols, probe_out, nprobe_out, pa.prow_out, t->build.cols, build_out, nbuild_out, pa.brow_out, outer,
+                head_type == QE_JOIN_LEFT, kGatherBlocksWide);   // (no launch for no rows: launch_gather_rows returns at once, as before)
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->join_stats.store(t->m, n, total, (int64_t)(uint32_t)h_ctl[1]);
+    ctx->join_stats.store(t->m, n, nout, (int64_t)(uint32_t)h_ctl[1]);
+    if (outer) ctx->outer_stats.store(1, total, tail, nbuild - tail);
     return res.release();
 }
 
@@ -258,6 +280,8 @@ int32_t qe_join_probe(qe_ctx *ctx, const qe_join_table *table, const qe_join_inp
 }
 
 int32_t qe_ctx_last_join_stats(const qe_ctx *ctx, int64_t out[4]) { return last_stats(ctx, &qe_ctx::join_stats, out); }
+
+int32_t qe_ctx_last_outer_stats(const qe_ctx *ctx, int64_t out[4]) { return last_stats(ctx, &qe_ctx::outer_stats, out); }
 
 int32_t qe_batch_from_result(qe_ctx *ctx, const qe_result *result, qe_batch **out) {
     if (out) *out = nullptr;

@@ -10,9 +10,15 @@
 //         counts the entries whose EVERY image is equal; (2) after an exclusive 64-bit scan of the counts the same walk
 //         writes (probe row, build row) pairs at the scanned offsets.  The order of the output is therefore the order of
 //         a nested loop with the probe side outside, whatever the order in which the waves run; the only atomics are an
-//         integer add (rows with a key) and an integer max (longest bucket), both independent of arrival order.
-// GATHER  one launch of the shared gathers (qe_kernels.hip) per output column through the pair lists; build row 0xFFFFFFFF
-//         ("none", LEFT) gives a zeroed value and validity 0.
+//         integer add (rows with a key), an integer max (longest bucket) and an integer OR (OUTER), all independent of
+//         arrival order.
+// OUTER   RIGHT / FULL: pass 1 also ORs the bit of every build row it finds equal into a bitmap over build rows that belongs
+//         to the CALL (the table is read only); the bit is read first and the atomic skipped when it is set.  The final
+//         bitmap is the OR of the same bits in whatever order they arrive.  Complemented, ranked and compacted
+//         (qe_scan.h) it is the TAIL: the build rows nobody matched, ascending, appended to the pair lists with probe row
+//         0xFFFFFFFF.  With a null bitmap (the other four types) pass 1 is the instantiation without the marks.
+// GATHER  one launch of the shared gathers (qe_kernels.hip) per output column through the pair lists; row 0xFFFFFFFF
+//         ("none": the build row under LEFT / FULL, the probe row of a tail row) gives a zeroed value and validity 0.
 #include <hip/hip_runtime.h>
 
 #include "qe_kernels.h"
@@ -134,8 +140,9 @@ __device__ __forceinline__ bool entry_equal(const JoinTableView &t, u32 s, const
 }
 
 // pass 1: matches per probe row (LEFT: at least 1; SEMI / ANTI: 0 or 1), the sorted position of the first match, the sum of
-// every block of 256 rows
-__global__ void __launch_bounds__(256) join_count_kernel(const JoinProbeArgs a) {
+// every block of 256 rows.  MARK (RIGHT / FULL, a.matched set): also the marks of the matched build rows; the other types run
+// the instantiation without them, which is the kernel as it was
+template <bool MARK> __global__ void __launch_bounds__(256) join_count_kernel(const JoinProbeArgs a) {
     __shared__ u64 s_sum[4];
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     u32 cnt = 0, first = kNone, walked = 0;
@@ -149,6 +156,13 @@ __global__ void __launch_bounds__(256) join_count_kernel(const JoinProbeArgs a) 
             for (u32 s = s0; s < s1; ++s) {
                 ++walked;
                 if (entry_equal(a.t, s, img)) {   // a shared hash alone is never a match
+                    if (MARK) {   // the build row has been matched.  Many probe rows hit one build row and 64 build rows share
+                                  // a word: only a lane that still sees the bit clear goes to the atomic (a stale read costs
+                                  // an OR that changes nothing)
+                        const u32 r = a.t.rows[s];
+                        const u64 bit = 1ull << (r & 63);
+                        if (!(__atomic_load_n(a.matched + (r >> 6), __ATOMIC_RELAXED) & bit)) atomicOr(a.matched + (r >> 6), bit);
+                    }
                     if (cnt == 0) first = s;
                     ++cnt;
                     if (first_only) break;
@@ -215,6 +229,15 @@ __global__ void __launch_bounds__(256) join_write_kernel(const JoinProbeArgs a) 
         }
 }
 
+// RIGHT / FULL: matched -> unmatched, a lane per word; the last word keeps only the bits of real rows
+__global__ void __launch_bounds__(256) join_unmatched_kernel(u64 *words, i64 n, i64 nwords) {
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    for (i64 w = (i64)blockIdx.x * blockDim.x + threadIdx.x; w < nwords; w += stride) {
+        const i64 rem = n - w * 64;
+        words[w] = ~words[w] & (rem < 64 ? (1ull << rem) - 1ull : ~0ull);
+    }
+}
+
 inline unsigned capped_blocks(i64 n, i64 cap) {
     const i64 blocks = (n + 255) / 256;
     return (unsigned)(blocks < cap ? blocks : cap);
@@ -236,12 +259,19 @@ int64_t join_probe_blocks(int64_t n) { return (n + 255) / 256; }
 
 void launch_join_count(hipStream_t s, const JoinProbeArgs &a) {
     if (a.n <= 0) return;
-    hipLaunchKernelGGL(join_count_kernel, dim3((unsigned)join_probe_blocks(a.n)), dim3(256), 0, s, a);
+    if (a.matched) hipLaunchKernelGGL(join_count_kernel<true>, dim3((unsigned)join_probe_blocks(a.n)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(join_count_kernel<false>, dim3((unsigned)join_probe_blocks(a.n)), dim3(256), 0, s, a);
 }
 
 void launch_join_write(hipStream_t s, const JoinProbeArgs &a) {
     if (a.n <= 0 || a.total == 0) return;
     hipLaunchKernelGGL(join_write_kernel, dim3((unsigned)join_probe_blocks(a.n)), dim3(256), 0, s, a);
+}
+
+void launch_join_unmatched(hipStream_t s, unsigned long long *words, int64_t n) {
+    if (n <= 0) return;
+    const i64 nwords = (n + 63) / 64;
+    hipLaunchKernelGGL(join_unmatched_kernel, dim3(capped_blocks(nwords, 8192)), dim3(256), 0, s, (u64 *)words, (i64)n, nwords);
 }
 
 }  // namespace qe

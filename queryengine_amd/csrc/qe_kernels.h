@@ -128,10 +128,16 @@ struct JoinProbeArgs {
     unsigned int *longest;                  // max over the probe rows of the entries one row walked
     unsigned long long total;               // pass 2: pairs the lists hold
     unsigned int *prow_out, *brow_out;      // pass 2: the pairs (brow_out null for SEMI / ANTI; build row 0xFFFFFFFF = none)
+    unsigned long long *matched;            // RIGHT / FULL (join_type is then the head's, INNER / LEFT): pass 1 sets bit r of this
+                                            // zeroed bitmap over BUILD ROWS for every build row r it finds equal; null otherwise,
+                                            // and pass 1 is then the kernel without the marks
 };
 int64_t join_probe_blocks(int64_t n);       // entries of blocksum
 void launch_join_count(hipStream_t s, const JoinProbeArgs &a);
 void launch_join_write(hipStream_t s, const JoinProbeArgs &a);
+// RIGHT / FULL of the hash join and the range join: the `matched` bitmap over the n rows of the build / right side becomes the
+// bitmap of the rows NOBODY matched -- every word complemented, the bits past row n cleared; ceil(n / 64) whole words
+void launch_join_unmatched(hipStream_t s, unsigned long long *words, int64_t n);
 
 // ---- window functions over a sorted result (qe_window.hip) ----
 constexpr int kWinTileRows = 2048;    // T: rows of one scan tile (4 waves x 8 words of 64 rows)
@@ -306,17 +312,29 @@ struct RangeOrdinalArgs {
 void launch_range_ordinals(hipStream_t s, const RangeOrdinalArgs &a);
 // Per left row l < nleft: cnt[l] = ord_hi[l] - ord_lo[l] when both ordinals are there and the difference is positive, else 0;
 // emit[l] (emit null: not wanted) = the output rows of l, cnt[l] or (left_join) max(cnt[l], 1); bit l of keep = (cnt[l] != 0) !=
-// (anti != 0), whole words, the bits past nleft 0; *longest (zeroed by the caller) = max cnt[l], by an integer atomic max
+// (anti != 0), whole words, the bits past nleft 0; *longest (zeroed by the caller) = max cnt[l], by an integer atomic max.
+// cover (RIGHT / FULL; null otherwise): a zeroed u32 difference array of nright + 1 entries over the positions of rlist; a left
+// row with cnt[l] != 0 adds 1 at ord_lo[l] and subtracts 1 at ord_hi[l] (integer atomic adds modulo 2^32)
 struct RangeCountArgs {
-    long long nleft;
+    long long nleft, nright;
     int left_join, anti;
     const unsigned int *ord_lo, *ord_hi;
     unsigned int *cnt;
     long long *emit;
     unsigned long long *keep;
     unsigned int *longest;
+    unsigned int *cover;
 };
 void launch_range_counts(hipStream_t s, const RangeCountArgs &a);
+// RIGHT / FULL: scanned[p] = the exclusive u32 sum of the difference array before p, so list position p < nright is covered by
+// scanned[p + 1] left intervals; a covered position sets bit rlist[p] of `matched`, a zeroed bitmap over RIGHT ROWS
+struct RangeMarkArgs {
+    long long nright;
+    const unsigned int *scanned;            // nright + 1 entries
+    const unsigned int *rlist;
+    unsigned long long *matched;
+};
+void launch_range_mark(hipStream_t s, const RangeMarkArgs &a);
 // The load-balanced expansion: output row o < total belongs to the last emitting left row e with eoff[e] <= o; with l = erow[e]
 // (erow null: l = e) and k = o - eoff[e] it writes lrow[o] = l and rrow[o] = cnt[l] ? rlist[ord_lo[l] + k] : 0xFFFFFFFF.  eoff:
 // the first output row of each of the nemit emitting left rows, strictly ascending from 0, so a tile of kRangeExpandTile output

@@ -37,13 +37,25 @@ qe_result *run_range(qe_ctx *ctx, const TwoSidedCall &q, int32_t left_lo, int32_
     check_sides(q, values, 3);
     need_device(ctx);
     const int64_t nl = q.left->count, nr = q.right->count;
-    const bool pairs = q.join_type == QE_JOIN_INNER || q.join_type == QE_JOIN_LEFT, left_join = q.join_type == QE_JOIN_LEFT;
+    // RIGHT / FULL: the HEAD is the INNER / LEFT output, the TAIL the right rows that no left row matched
+    const bool outer = q.join_type == QE_JOIN_RIGHT || q.join_type == QE_JOIN_FULL;
+    const bool left_join = q.join_type == QE_JOIN_LEFT || q.join_type == QE_JOIN_FULL, pairs = left_join || outer || q.join_type == QE_JOIN_INNER;
 
     PoolScratch sc(ctx);
-    int64_t nout = 0, nemit = 0, longest = 0;
-    uint32_t *ord_lo = nullptr, *cnt = nullptr, *rlist = nullptr, *keep_prefix = nullptr;
+    int64_t nout = 0, nemit = 0, longest = 0, tail = 0;
+    uint32_t *ord_lo = nullptr, *cnt = nullptr, *rlist = nullptr, *keep_prefix = nullptr, *cover = nullptr, *tail_prefix = nullptr;
     long long *offset = nullptr;
-    unsigned long long *keep = nullptr;
+    unsigned long long *keep = nullptr, *unmatched = nullptr;
+    unsigned long long *d_ctl = (unsigned long long *)sc.alloc(32);   // [0] output rows of the head, [1] longest (u32), [2] kept left rows, [3] tail rows
+    QE_HIP(hipMemsetAsync(d_ctl, 0, 32, ctx->stream));
+    if (outer && nr > 0) {   // the marks over the right rows, and (both sides there) the difference array over the list positions
+        unmatched = (unsigned long long *)sc.alloc(bitmap_bytes(nr));
+        QE_HIP(hipMemsetAsync(unmatched, 0, bitmap_bytes(nr), ctx->stream));
+        if (nl > 0) {
+            cover = (uint32_t *)sc.alloc((size_t)(nr + 1) * 4);
+            QE_HIP(hipMemsetAsync(cover, 0, (size_t)(nr + 1) * 4, ctx->stream));
+        }
+    }
     if (nl > 0) {
         // ---- 1. the two ordinals of every left row.  Ties fall by the order of the concatenation, as in the ASOF join: an
         // inclusive lower end counts only the right rows BELOW lo (left rows first), an inclusive upper end also those equal
@@ -63,11 +75,11 @@ qe_result *run_range(qe_ctx *ctx, const TwoSidedCall &q, int32_t left_lo, int32_
         // (ANTI) a match as a bitmap with its ranks ----
         cnt = (uint32_t *)sc.alloc((size_t)nl * 4);
         keep = (unsigned long long *)sc.alloc(bitmap_bytes(nl));
-        unsigned long long *d_ctl = (unsigned long long *)sc.alloc(32);   // [0] output rows, [1] longest (u32), [2] kept left rows
-        QE_HIP(hipMemsetAsync(d_ctl, 0, 32, ctx->stream));
         if (pairs) offset = (long long *)sc.alloc((size_t)nl * 8);
         RangeCountArgs ca{};
         ca.nleft = nl;
+        ca.nright = nr;
+        ca.cover = cover;
         ca.left_join = left_join ? 1 : 0;
         ca.anti = q.join_type == QE_JOIN_ANTI ? 1 : 0;
         ca.ord_lo = ord_lo;
@@ -86,6 +98,25 @@ qe_result *run_range(qe_ctx *ctx, const TwoSidedCall &q, int32_t left_lo, int32_
             keep_prefix = (uint32_t *)sc.alloc((size_t)(bitmap_words(nl) + 1) * 4);
             bitmap_ranks(ctx->stream, (const uint64_t *)keep, nullptr, nl, keep_prefix, sums, d_ctl + (pairs ? 2 : 0));
         }
+    }
+    if (unmatched) {
+        // ---- 2a. RIGHT / FULL: difference array -> cover counts -> marks -> the unmatched right rows and their ranks ----
+        if (cover) {
+            uint32_t *sums = (uint32_t *)sc.alloc((size_t)scan_blocks(nr + 1) * 4);
+            exclusive_scan<u32>(ctx->stream, ArrayLoad<u32>{cover}, cover, sums, nr + 1, nullptr);   // in place
+            RangeMarkArgs ma{};
+            ma.nright = nr;
+            ma.scanned = cover;
+            ma.rlist = rlist;
+            ma.matched = unmatched;
+            launch_range_mark(ctx->stream, ma);
+        }
+        uint32_t *sums = (uint32_t *)sc.alloc((size_t)scan_blocks(bitmap_words(nr) + 1) * 4);
+        tail_prefix = (uint32_t *)sc.alloc((size_t)(bitmap_words(nr) + 1) * 4);
+        launch_join_unmatched(ctx->stream, unmatched, nr);
+        bitmap_ranks(ctx->stream, (const uint64_t *)unmatched, nullptr, nr, tail_prefix, sums, d_ctl + 3);
+    }
+    if (nl > 0 || unmatched) {
         unsigned long long h_ctl[4] = {0, 0, 0, 0};
         QE_HIP(hipMemcpyAsync(h_ctl, d_ctl, 32, hipMemcpyDeviceToHost, ctx->stream));   // the one read-back besides the sorts' own
         QE_HIP(hipGetLastError());
@@ -94,20 +125,23 @@ qe_result *run_range(qe_ctx *ctx, const TwoSidedCall &q, int32_t left_lo, int32_
                                     // reported by the pool below (QE_ERR_OOM)
         longest = (int64_t)(uint32_t)h_ctl[1];
         nemit = left_join ? nl : pairs ? (int64_t)h_ctl[2] : nout;
+        tail = (int64_t)h_ctl[3];
+        if (tail < 0 || tail > nr) fail(QE_ERR_INTERNAL, std::string(q.who) + ": " + std::to_string(tail) + " unmatched of " + std::to_string(nr) + " right rows");
         if (nout < 0 || nemit < 0 || nemit > nl || longest > nr || (nout > 0 && nemit == 0) || (!pairs && nout > nl))
             fail(QE_ERR_INTERNAL, std::string(q.who) + ": " + std::to_string(nout) + " output rows from " + std::to_string(nemit) + " of " +
                                       std::to_string(nl) + " left rows, longest " + std::to_string(longest));
     }
 
     // ---- 3. the row lists: the kept left rows (SEMI / ANTI), or the expansion into pairs (INNER / LEFT) ----
-    ResultPtr res = new_result(ctx, nout);
+    const int64_t nrows = nout + tail;
+    ResultPtr res = new_result(ctx, nrows);
     uint32_t *lrows = nullptr, *rrows = nullptr;
-    if (nout > 0) {
-        lrows = (uint32_t *)sc.alloc((size_t)nout * 4);
+    if (nrows > 0) {
+        lrows = (uint32_t *)sc.alloc((size_t)nrows * 4);
         if (!pairs) {
             bitmap_positions(ctx->stream, (const uint64_t *)keep, nullptr, nl, keep_prefix, lrows, nout, false);
         } else {
-            rrows = (uint32_t *)sc.alloc((size_t)nout * 4);
+            rrows = (uint32_t *)sc.alloc((size_t)nrows * 4);
             RangeExpandArgs xa{};
             xa.total = nout;
             xa.nemit = nemit;
@@ -127,16 +161,21 @@ qe_result *run_range(qe_ctx *ctx, const TwoSidedCall &q, int32_t left_lo, int32_
             xa.rlist = rlist;
             xa.lrow = lrows;
             xa.rrow = rrows;
-            launch_range_expand(ctx->stream, xa);
+            launch_range_expand(ctx->stream, xa);   // (no launch for an empty head)
+        }
+        if (tail > 0) {   // the tail extends the two lists: no left row, the unmatched right rows ascending
+            QE_HIP(hipMemsetAsync(lrows + nout, 0xFF, (size_t)tail * 4, ctx->stream));
+            bitmap_positions(ctx->stream, (const uint64_t *)unmatched, nullptr, nr, tail_prefix, rrows + nout, tail, false);
         }
     }
 
     // ---- 4. the output: the listed left columns by the left rows, the listed right columns by their matches ----
-    emit_joined(ctx, res.get(), nout, q.left->cols, q.left_out, q.nleft_out, lrows, q.right->cols, q.right_out, q.nright_out, rrows, left_join,
-                kGatherBlocksWide);
+    emit_joined(ctx, res.get(), nrows, q.left->cols, q.left_out, q.nleft_out, lrows, q.right->cols, q.right_out, q.nright_out, rrows, outer,
+                left_join, kGatherBlocksWide);
     QE_HIP(hipGetLastError());
     QE_HIP(hipStreamSynchronize(ctx->stream));   // the scratch goes back to the pool now
-    ctx->range_stats.store(nl, nr, nout, longest);
+    ctx->range_stats.store(nl, nr, nrows, longest);
+    if (outer) ctx->outer_stats.store(2, nout, tail, nr - tail);
     return res.release();
 }
 

@@ -13,8 +13,15 @@
 //              to the tile, and every lane finds the left row of its output row by a binary search there.  No lane walks a
 //              left row's matches: the work per output row is the search, whatever the counts are, and the stores of a wave
 //              are 256 contiguous bytes.
-// Bitmap words come from __ballot and are written by lane 0 of each wave; a lane past the last row votes 0.  The one atomic is
-// the integer max of the counts, which feeds the stats only.
+//   cover      RIGHT / FULL only.  The matched right rows are the union of the intervals R[lo .. hi) of the left rows.  `counts`
+//              adds +1 at lo and -1 at hi of every left row with a match into a zeroed DIFFERENCE ARRAY over the list positions:
+//              u32, modulo 2^32 -- a position is covered by at most nleft < 2^32 intervals, so the scanned value is exact.  The
+//              shared exclusive scan turns it into the cover count of every position, and `mark` sets the bit of right row R[p]
+//              for every covered p in a bitmap over right rows (two positions may share a word: an integer OR).  Complemented
+//              (launch_join_unmatched), ranked and compacted it is the tail of the output.
+// Bitmap words come from __ballot and are written by lane 0 of each wave; a lane past the last row votes 0.  The atomics are
+// the integer max of the counts, which feeds the stats only, and under RIGHT / FULL the integer adds of the difference array
+// and the integer ORs of the marks: the final value of each is the same in whatever order they arrive.
 #include <hip/hip_runtime.h>
 
 #include "qe_kernels.h"
@@ -65,6 +72,10 @@ __global__ void __launch_bounds__(256) range_counts(const RangeCountArgs a) {
             const u32 lo = a.ord_lo[l], hi = a.ord_hi[l];
             if (lo != kNoRow && hi != kNoRow && hi > lo) c = hi - lo;
             a.cnt[l] = c;
+            if (a.cover && c != 0 && (i64)hi <= a.nright) {   // RIGHT / FULL (the same in every lane): [lo, hi) is covered once more
+                atomicAdd(a.cover + lo, 1u);
+                atomicAdd(a.cover + hi, 0xFFFFFFFFu);   // -1 modulo 2^32
+            }
             if (a.emit) a.emit[l] = (a.left_join && c == 0) ? 1ll : (i64)c;
         }
         most = c > most ? c : most;
@@ -81,6 +92,20 @@ __global__ void __launch_bounds__(256) range_counts(const RangeCountArgs a) {
 void launch_range_counts(hipStream_t s, const RangeCountArgs &a) {
     if (a.nleft <= 0) return;
     hipLaunchKernelGGL(range_counts, dim3(range_grid(a.nleft)), dim3(256), 0, s, a);
+}
+
+// ---- RIGHT / FULL: the covered list positions as marks over the right rows ---------------------------------------------------------
+__global__ void __launch_bounds__(256) range_mark(const RangeMarkArgs a) {
+    const i64 stride = (i64)gridDim.x * 256;
+    for (i64 p = (i64)blockIdx.x * 256 + threadIdx.x; p < a.nright; p += stride) {
+        if (a.scanned[p + 1] == 0) continue;   // the sum of the differences up to and including p: the intervals that hold p
+        const i64 r = a.rlist[p];              // (a covered position is below the number of eligible right rows: rlist[p] is written)
+        if (r < a.nright) atomicOr(a.matched + (r >> 6), 1ull << (r & 63));
+    }
+}
+void launch_range_mark(hipStream_t s, const RangeMarkArgs &a) {
+    if (a.nright <= 0) return;
+    hipLaunchKernelGGL(range_mark, dim3(range_grid(a.nright)), dim3(256), 0, s, a);
 }
 
 // ---- the expansion of the counts into (left row, right row) pairs ----------------------------------------------------------------

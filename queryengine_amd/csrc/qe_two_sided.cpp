@@ -10,7 +10,7 @@ void check_call(const TwoSidedCall &q, uint32_t join_types, const char *option_e
     if (q.nby < 0 || q.nby > 7) fail(QE_ERR_INVALID_ARG, who + "0 to 7 by columns");   // with the value column: the sort's 8 keys
     if (q.nby > 0 && (!q.left_by || !q.right_by)) fail(QE_ERR_INVALID_ARG, who + "by columns missing");
     if (option_error) fail(QE_ERR_INVALID_ARG, who + option_error);
-    if (q.join_type < 0 || q.join_type > QE_JOIN_ANTI || !((join_types >> q.join_type) & 1u))
+    if (q.join_type < 0 || q.join_type > QE_JOIN_FULL || !((join_types >> q.join_type) & 1u))   // (4 to 7 are in no set)
         fail(QE_ERR_INVALID_ARG, who + (join_types == kJoinsAll ? "unknown join type" : "the join type is INNER or LEFT"));
     if (q.nleft_out < 0 || q.nright_out < 0) fail(QE_ERR_INVALID_ARG, who + "negative column count");
     if ((q.nleft_out > 0 && !q.left_out) || (q.nright_out > 0 && !q.right_out)) fail(QE_ERR_INVALID_ARG, who + "output columns missing");

@@ -210,9 +210,15 @@ class Context:
         return JoinTable(self, side, key_cols)
 
     def last_join_stats(self) -> List[int]:
-        """qe_ctx_last_join_stats: [build rows in the table, probe rows, output rows, longest candidate run one probe row
-        scanned] of the last join_build / probe on this context."""
+        """qe_ctx_last_join_stats: [build rows in the table, probe rows, output rows (JOIN_RIGHT / JOIN_FULL: head + tail),
+        longest candidate run one probe row scanned] of the last join_build / probe on this context."""
         return self._last_stats(self._lib.qe_ctx_last_join_stats)
+
+    def last_outer_stats(self) -> List[int]:
+        """qe_ctx_last_outer_stats: [1 = hash probe / 2 = range join, head rows, tail rows, build / right rows matched at least
+        once] of the last JOIN_RIGHT or JOIN_FULL call on this context; zeros before the first, and the other join types leave
+        it alone.  Tail rows + matched rows = the rows of the build / right side."""
+        return self._last_stats(self._lib.qe_ctx_last_outer_stats)
 
     def window(self, result: "Result", partition_by: Sequence[int], order_by: Sequence, functions: Sequence) -> "Result":
         """qe_result_window / qe_result_window_frames: every row of `result`, sorted stably by `partition_by` (columns,
@@ -300,7 +306,8 @@ class Context:
         order_by_keys compares, a NULL bound or `on` matches nothing).  The listed left columns, then the listed right columns:
         left rows in input order, the matches of one left row ascending by `on`, ties in right row order.  JOIN_INNER the pairs;
         JOIN_LEFT also a row with NULL right columns for a left row without a match; JOIN_SEMI / JOIN_ANTI the left rows with /
-        without a match, once, and no right columns."""
+        without a match, once, and no right columns.  JOIN_RIGHT / JOIN_FULL: the JOIN_INNER / JOIN_LEFT rows, then every right
+        row that no left row matched, ascending by right row, with NULL left columns (last_outer_stats())."""
         h = C.c_void_p()
         N.check(self.handle, self._lib.qe_result_range_join(
             self.handle, left.handle, right.handle, _i32_array(left_by), _i32_array(right_by), len(left_by), int(left_lo), int(left_hi),
@@ -476,7 +483,9 @@ class JoinTable:
 
     def probe(self, side, key_cols: Sequence[int], join_type: int = N.JOIN_INNER, probe_out: Sequence[int] = (),
               build_out: Sequence[int] = ()) -> "Result":
-        """qe_join_probe: the listed probe columns, then the listed build columns, in nested-loop order (probe outside)."""
+        """qe_join_probe: the listed probe columns, then the listed build columns, in nested-loop order (probe outside).
+        JOIN_RIGHT / JOIN_FULL: the JOIN_INNER / JOIN_LEFT rows, then every build row that no probe row of this call matched,
+        ascending by build row, with NULL probe columns; the table itself is not changed (last_outer_stats())."""
         h = C.c_void_p()
         inp = _join_input(side)
         N.check(self.ctx.handle, self.ctx._lib.qe_join_probe(

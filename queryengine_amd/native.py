@@ -33,6 +33,7 @@ FORM_GROUPBY_DENSE, FORM_GROUPBY_HASHED, FORM_GROUPBY_HASH_PARTITIONED = 8, 9, 1
 GROUPBY_ROUTES = ("none", "dense_lds", "dense_key_range", "dense_global", "hashed", "dense_ids", "hash_partitioned_host",
                   "hash_partitioned_device")
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = range(4)
+JOIN_RIGHT, JOIN_FULL = 8, 9                 # head (INNER / LEFT rows) + tail (unmatched build / right rows); 4 to 7 are unassigned
 WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_SUM, WIN_COUNT, WIN_MIN, WIN_MAX, WIN_AVG, WIN_LAG, WIN_LEAD = range(10)
 WIN_FIRST_VALUE, WIN_LAST_VALUE = 10, 11        # qe_result_window_frames only
 FRAME_UNBOUNDED = -1                             # QE_FRAME_UNBOUNDED: a frame edge at the partition's edge
@@ -178,6 +179,7 @@ SYMBOLS = [
     ("qe_join_probe", C.c_int32, [_P, _P, C.POINTER(JoinInput), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                   C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_P)]),
     ("qe_ctx_last_join_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
+    ("qe_ctx_last_outer_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),
     ("qe_result_window", C.c_int32, [_P, _P, C.POINTER(C.c_int32), C.c_int32, _P, C.c_int32, C.POINTER(WindowFn), C.c_int32, C.POINTER(_P)]),
     ("qe_result_window_frames", C.c_int32, [_P, _P, C.POINTER(C.c_int32), C.c_int32, _P, C.c_int32, C.POINTER(WindowFrameFn), C.c_int32, C.POINTER(_P)]),
     ("qe_ctx_last_window_stats", C.c_int32, [_P, C.POINTER(C.c_int64)]),

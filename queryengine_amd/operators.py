@@ -228,15 +228,19 @@ def _join_key(values: Sequence[Any]):
 
 class _TwoSidedJoinOperator(DeviceResultOperator):
     """What the joins of two sources share: the checks of the key and output lists and of the join type, the draining of the
-    two sources (once when they are one object), the width of the NULL tail of a LEFT join, and the loop that turns "the right
-    rows this left row matches" (``_matches``, over what ``_index`` made of the right rows) into INNER / LEFT / SEMI / ANTI rows:
-    left-row order, the matches of one row in the order ``_matches`` gives them, an unmatched LEFT row in its place with every
-    right column ``None``.  A subclass names its public attributes: ``<side>``, ``<side>_<key word>`` and ``<side>_out``."""
+    two sources (once when they are one object), the width of the NULL side of a LEFT / RIGHT / FULL join, and the loop that
+    turns "the right rows this left row matches" (``_matches``, over what ``_index`` made of the right rows) into INNER / LEFT /
+    SEMI / ANTI rows: left-row order, the matches of one row in the order ``_matches`` gives them, an unmatched LEFT row in its
+    place with every right column ``None``.  RIGHT / FULL are the INNER / LEFT rows followed by the right rows that
+    ``_matches`` never returned, in right-row order, each with ``None`` for every left column; they are told apart by their
+    POSITION in the right source, so two equal right rows are two rows.  A subclass names its public attributes: ``<side>``,
+    ``<side>_<key word>`` and ``<side>_out``."""
 
     _sides = ("left", "right")
     _key_word = "by"
     _key_counts = (0, 7)
-    _join_types: Sequence[int] = (N.JOIN_INNER, N.JOIN_LEFT, N.JOIN_SEMI, N.JOIN_ANTI)
+    _join_types: Sequence[int] = (N.JOIN_INNER, N.JOIN_LEFT, N.JOIN_SEMI, N.JOIN_ANTI, N.JOIN_RIGHT, N.JOIN_FULL)
+    _join_type_error = "unknown join type"
 
     def __init__(self, left: Operator, right: Operator, left_by: Sequence[int], right_by: Sequence[int], join_type: int,
                  left_out: Optional[Sequence[int]], right_out: Optional[Sequence[int]]):
@@ -247,9 +251,11 @@ class _TwoSidedJoinOperator(DeviceResultOperator):
         if not fewest <= len(self._by[0]) <= most or len(self._by[0]) != len(self._by[1]):
             raise ValueError(f"{name}: {fewest} to {most} {self._key_word} columns, as many on the {lname} side as on the {rname} side")
         if isinstance(join_type, bool) or join_type not in self._join_types:
-            raise ValueError(f"{name}: " + ("unknown join type" if len(self._join_types) == 4 else "the join type is INNER or LEFT"))
+            raise ValueError(f"{name}: {self._join_type_error}")
         self.join_type = int(join_type)
-        self._pairs = self.join_type in (N.JOIN_INNER, N.JOIN_LEFT)
+        self._outer = self.join_type in (N.JOIN_RIGHT, N.JOIN_FULL)                   # a tail of unmatched right rows
+        self._keeps_left = self.join_type in (N.JOIN_LEFT, N.JOIN_FULL)               # an unmatched left row stays, in its place
+        self._pairs = self._outer or self.join_type in (N.JOIN_INNER, N.JOIN_LEFT)
         if not self._pairs and right_out:
             raise ValueError(f"{name}: a SEMI / ANTI join has no {rname} columns")
         self._out = [None if out is None else [int(c) for c in out] for out in (left_out, right_out)]
@@ -284,16 +290,22 @@ class _TwoSidedJoinOperator(DeviceResultOperator):
                 right_out = []
             elif right_rows:
                 right_out = list(range(len(right_rows[0])))
-            elif self.join_type == N.JOIN_LEFT and left_rows:
-                rname = self._sides[1]
-                raise ValueError(f"{type(self).__name__}: {rname}_out must be given when a LEFT join's {rname} source yields no row")
+            elif self._keeps_left and left_rows:
+                rname, jname = self._sides[1], "FULL" if self._outer else "LEFT"
+                raise ValueError(f"{type(self).__name__}: {rname}_out must be given when a {jname} join's {rname} source yields no row")
             else:
                 right_out = []
+        if left_out is None and self._outer and right_rows and not left_rows:   # the whole right side is the tail: how many Nones?
+            lname, jname = self._sides[0], "FULL" if self._keeps_left else "RIGHT"
+            raise ValueError(f"{type(self).__name__}: {lname}_out must be given when a {jname} join's {lname} source yields no row")
         index = self._index(right_rows)
         out = []
+        returned = set()   # RIGHT / FULL: id() of the right rows _matches has returned -- the row objects of right_rows, one per position
         for row in left_rows:
             head = [row[c] for c in (range(len(row)) if left_out is None else left_out)]
             matches = self._matches(row, index)
+            if self._outer:
+                returned.update(id(m) for m in matches)
             if self.join_type == N.JOIN_SEMI:
                 if matches:
                     out.append(head)
@@ -302,18 +314,24 @@ class _TwoSidedJoinOperator(DeviceResultOperator):
                     out.append(head)
             elif matches:
                 out.extend(head + [m[c] for c in right_out] for m in matches)
-            elif self.join_type == N.JOIN_LEFT:
+            elif self._keeps_left:
                 out.append(head + [None] * len(right_out))
+        if self._outer:
+            nleft = len(left_rows[0]) if left_out is None and left_rows else len(left_out or ())
+            out.extend([None] * nleft + [r[c] for c in right_out] for r in right_rows if id(r) not in returned)
         return out
 
 
 class HashJoinOperator(_TwoSidedJoinOperator):
     """Equi-join of a probe source against a build source: ``probe_keys[i]`` pairs with ``build_keys[i]`` (column
-    indices).  ``join_type`` is ``native.JOIN_INNER / JOIN_LEFT / JOIN_SEMI / JOIN_ANTI``.  A row is the listed probe
-    columns followed by the listed build columns (``None`` = every column of that side; SEMI and ANTI have no build
-    columns); rows come in the order of a nested loop with the probe side outside: probe-row order, the matches of one
-    probe row in build-row order, an unmatched LEFT row in its place with every build column ``None``.  The reference
-    has no join (Query.g4 reads one table); the operator follows ``OrderByOperator``.
+    indices).  ``join_type`` is ``native.JOIN_INNER / JOIN_LEFT / JOIN_SEMI / JOIN_ANTI / JOIN_RIGHT / JOIN_FULL``.  A row is
+    the listed probe columns followed by the listed build columns (``None`` = every column of that side; SEMI and ANTI have
+    no build columns); rows come in the order of a nested loop with the probe side outside: probe-row order, the matches of
+    one probe row in build-row order, an unmatched LEFT row in its place with every build column ``None``.  ``JOIN_RIGHT``
+    is the INNER rows and ``JOIN_FULL`` the LEFT rows, each followed by every build row that no probe row matched (a build
+    row with a ``None`` key among them), once, in build-row order, every probe column ``None``; ``probe_out`` must be given
+    when the probe source yields no row, as ``build_out`` must under LEFT / FULL when the build source yields none.  The
+    reference has no join (Query.g4 reads one table); the operator follows ``OrderByOperator``.
 
     When both sources are GPU operators of one context (``result()`` and ``ctx``), the join runs on the device
     (qe_join_build + qe_join_probe) and the operator offers ``result()`` and ``ctx`` itself, so an ``OrderByOperator`` on top
@@ -691,7 +709,8 @@ class AsofJoinOperator(_TwoSidedJoinOperator):
     host by a plain nested loop over ``_join_key`` and ``_compare_key`` -- the executable statement of the semantics, written
     for clarity, and the expectation of the device tests."""
 
-    _join_types = (N.JOIN_INNER, N.JOIN_LEFT)
+    _join_types = (N.JOIN_INNER, N.JOIN_LEFT)   # a FULL ASOF join has no accepted meaning
+    _join_type_error = "the join type is INNER or LEFT"
 
     def __init__(self, left: Operator, right: Operator, left_by: Sequence[int], right_by: Sequence[int], left_on: int, right_on: int,
                  direction: int = N.ASOF_BACKWARD, strict: bool = False, join_type: int = N.JOIN_LEFT,
@@ -751,8 +770,11 @@ class RangeJoinOperator(_TwoSidedJoinOperator):
     A row is the listed left columns followed by the listed right columns (``None`` = every column of that side; SEMI and ANTI
     have no right columns).  Left rows come in input order, the matches of one left row ascending by ``on``, ties in right row
     order: ``native.JOIN_INNER`` the pairs, ``JOIN_LEFT`` also a row with every right column ``None`` for a left row without a
-    match, ``JOIN_SEMI`` / ``JOIN_ANTI`` the left rows with / without a match, once.  ``left`` and ``right`` may be the same
-    operator; it is then drained once.  The reference has no join (Query.g4 reads one table).
+    match, ``JOIN_SEMI`` / ``JOIN_ANTI`` the left rows with / without a match, once.  ``JOIN_RIGHT`` is the INNER rows and
+    ``JOIN_FULL`` the LEFT rows, each followed by every right row that no left row matched (a right row with a ``None`` by
+    column or ``on`` among them), once, in right row order, every left column ``None``; ``left_out`` must be given when the
+    left source yields no row.  ``left`` and ``right`` may be the same operator; it is then drained once.  The reference has
+    no join (Query.g4 reads one table).
 
     When both sources are GPU operators of one context (``result()`` and ``ctx``) the rows never leave HBM
     (qe_result_range_join) and the operator offers ``result()`` and ``ctx`` itself.  Any other pair is drained and joined on the

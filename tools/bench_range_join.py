@@ -16,7 +16,11 @@ measured round is listed below the tables.
 3. Same output, different shape.  2^20 left rows against 2^24 right rows with the distinct values 0 .. 2^24 - 1, no by column,
    2^24 output rows: once every left row takes 16 of them, once one left row takes them all and the others ask for nothing.
 
-    python tools/bench_range_join.py [--rows 1048576,4194304,16777216] [--reps 5] [--warmup 1] [--out profiles/range_join_summary.txt]"""
+--join-types lists the forms of parts 1 and 2 (INNER, LEFT, RIGHT, FULL); under RIGHT / FULL part 2 also compares the tails of
+the two joins byte for byte.
+
+    python tools/bench_range_join.py [--rows 1048576,4194304,16777216] [--join-types INNER,LEFT] [--reps 5] [--warmup 1]
+                                     [--out profiles/range_join_summary.txt]"""
 import argparse
 import os
 import sys
@@ -32,6 +36,11 @@ from queryengine_amd import native as N  # noqa: E402
 
 I32, I64, F64 = DataType.INT32, DataType.INT64, DataType.DOUBLE
 INNER, LEFT = N.JOIN_INNER, N.JOIN_LEFT
+JOIN_TYPES = {"INNER": INNER, "LEFT": LEFT, "RIGHT": N.JOIN_RIGHT, "FULL": N.JOIN_FULL}
+
+
+def forms(a):
+    return [(JOIN_TYPES[t.strip().upper()], t.strip().upper()) for t in a.join_types.split(",")]
 
 
 def spec(kind, col_id, modulus=0, offset=0):
@@ -98,7 +107,7 @@ def own_cost(ctx, a, lines, runs):
             w = matches * 1000.0 / n
             left = generated(ctx, [spec(N.GEN_I32_MOD, 0, 1000), spec(N.GEN_F64_UNIT, 7), spec(N.GEN_I64_ROWID, 8)], n, 17,
                              [col(0, I32), col(1, F64), fn(Function.ADD, col(1, F64), w), col(2, I64)])
-            for join_type, form in ((INNER, "INNER"), (LEFT, "LEFT")):
+            for join_type, form in forms(a):
                 calls = [("range", lambda: ctx.range_join(left, right, [0], [0], 1, 2, 1, False, False, join_type, [3], [2])),
                          ("sorts", lambda: [ctx.order_by_keys(keys_only, [(0, False), (1, False)]) for _ in range(2)])]
                 ms, rows = rounds(ctx, calls, a.reps, a.warmup)
@@ -131,7 +140,7 @@ def heavy_hitter(ctx, a, lines, runs):
 
     for name, lheavy, rheavy in (("one key on 1/4 of the right rows", 64, n // 4), ("uniform", 0, 0)):
         left, right = side(lheavy, 17), side(rheavy, 23)
-        for join_type, form in ((INNER, "INNER"), (LEFT, "LEFT")):
+        for join_type, form in forms(a):
             def hashed():
                 table = ctx.join_build(right, [0])
                 try:
@@ -189,6 +198,7 @@ def same_output(ctx, a, lines, runs):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rows", default="1048576,4194304,16777216", help="rows per side of part 1, one run of every case each")
+    ap.add_argument("--join-types", default="INNER,LEFT", help="forms of parts 1 and 2, comma-separated: " + ", ".join(JOIN_TYPES))
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--parts", default="1,2,3")
